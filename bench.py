@@ -16,6 +16,12 @@ path on one pre-generated device-resident chunk:
 Launch: python bench.py --gpus N --steps K --warmup W
 (for N>1 the driver uses torch.distributed.run; RANK/LOCAL_RANK/WORLD_SIZE
 are read from the env). Rank 0 prints ONE json line per the bench contract.
+
+A plain run does only what the headline figure needs: setup, warmup,
+priming, the K timed steps, the result line. --full adds the secondary
+measurements (p50 single-channel latency, in-loop GPU-busy sampling);
+their result fields are null without it. --dump-outputs DIR writes what
+the last timed step produced as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import datetime as dt
@@ -66,6 +72,12 @@ def main():
                          "variant: 250 exercises >100-comment posts)")
     ap.add_argument("--cpu", action="store_true",
                     help="debug: run the Python golden path on CPU (tiny)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements (p50 "
+                         "single-channel latency, GPU-busy sampling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to "
+                         "DIR/<name>.npy (float32/float64, <= 64 MB)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -213,6 +225,9 @@ def main():
 
     total_out_bytes = 0
     new_discoveries = 0
+    # --dump-outputs: what the last timed step handed to its caller
+    last_si = args.warmup + args.steps - 1
+    last_out = {}
 
     def step(si):
         nonlocal total_out_bytes, new_discoveries
@@ -234,8 +249,14 @@ def main():
                     seen.merge_remote(new_hashes, torch.distributed,
                                       world)
                 nd = seen.new_count()  # syncs within the compute stream
+                if args.dump_outputs and si == last_si:
+                    last_out.update(
+                        line_off=res.line_off, line_len=res.line_len,
+                        link_cnt=res.link_cnt, link_hash=res.link_hash)
             else:
                 out_t, _off, _len = gpu.yt_parse_encode(chunk, now=now)
+                if args.dump_outputs and si == last_si:
+                    last_out.update(line_off=_off, line_len=_len)
                 if world > 1:
                     # mixed dispatch still exchanges (empty) discovery
                     # buffers so collectives stay symmetric across ranks
@@ -271,6 +292,8 @@ def main():
         inflight[slot] = (out_t, dones)
         total_out_bytes += nbytes
         new_discoveries += nd
+        if args.dump_outputs and si == last_si:
+            last_out.update(jsonl=pinned[slot][:nbytes], new_discoveries=nd)
         if sink_f is not None:
             for d in dones:
                 d.synchronize()
@@ -285,7 +308,7 @@ def main():
     # ---- p50 channel latency (BASELINE secondary metric): one channel's
     # batch through the full pipeline (parse+encode -> claim -> D2H) ----
     p50_channel_ms = None
-    if my_platform == "telegram":
+    if args.full and my_platform == "telegram":
         lat = []
         one = feed.build_batch_device(
             np.array([999_990 + rank]), device, posts_per_channel=args.posts
@@ -330,6 +353,8 @@ def main():
     stop_busy = _threading.Event()
     busy_paths = sorted(_glob.glob(
         "/sys/class/drm/card*/device/gpu_busy_percent"))
+    if not args.full:
+        busy_paths = []  # secondary measurement: sampler never starts
 
     def _busy_sampler():
         while not stop_busy.is_set():
@@ -346,7 +371,8 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     torch.cuda.synchronize()
-    sampler.start()
+    if busy_paths:
+        sampler.start()
     step_times = []
     t0 = time.perf_counter()
     for si in range(args.steps):
@@ -399,6 +425,11 @@ def main():
     if sink_f is not None:
         sink_f.close()
 
+    if args.dump_outputs and rank == 0 and last_out:
+        # after the timed region's final synchronize: the host ring slot
+        # and the device tensors of the last step are complete
+        dump_outputs(args.dump_outputs, last_out)
+
     if rank == 0:
         result = {
             "metric": "posts/sec (whole node) synthetic feed",
@@ -448,6 +479,89 @@ def main():
 
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+DUMP_SEED = 20260101
+DUMP_MAX_ROWS = 1_250_000       # per-row arrays: one flagship step, whole
+DUMP_HASH_ROWS = 65_536
+DUMP_WINDOWS, DUMP_WINDOW = 128, 32_768
+DUMP_BLOCK = 1 << 20
+
+
+def dump_outputs(dirpath, last):
+    """Write the last timed step's outputs as float32/float64 .npy files.
+
+    The step hands its caller the JSONL bytes in the host ring plus the
+    per-post line table and extracted links; a flagship step is 2.5 GB
+    of JSONL, so the files stay under 64 MB in all by sampling with a
+    fixed seed (same arguments -> same inputs, rows and windows):
+
+      jsonl_block_sums  f64  sum of every 1 MiB block of the JSONL bytes
+                             (covers every byte), last entry = tail
+      jsonl_sample      f32  128 seeded 32 KiB windows of the JSONL bytes
+                             (all bytes if the output is smaller)
+      line_off          f64  per post: every post of a step of up to
+      line_len          f32  DUMP_MAX_ROWS, else a seeded sorted row sample
+      link_cnt          f32  (telegram) same rows
+      link_hash         f64  (telegram) [rows, MAX_LINKS, 2] = high and
+                             low 32 bits of the fnv1a64 link hashes, for
+                             a seeded sample of DUMP_HASH_ROWS posts
+      new_discoveries   f64  [1] first-time links claimed by the step
+
+    The per-link new_mask is left out: which of two posts carrying the
+    same new link wins the atomicCAS claim is a race; the count is not.
+    """
+    os.makedirs(dirpath, exist_ok=True)
+
+    def save(name, arr):
+        assert arr.dtype in (np.float32, np.float64)
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+        return arr.nbytes
+
+    def rows_of(n, cap):
+        if n <= cap:
+            return None
+        rng = np.random.default_rng([DUMP_SEED, cap])
+        return np.sort(rng.choice(n, size=cap, replace=False))
+
+    def take(t, rows):
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        return t.cpu().numpy()
+
+    total = 0
+    jsonl = last["jsonl"].numpy()
+    nbytes = jsonl.shape[0]
+    nblk = nbytes // DUMP_BLOCK
+    sums = jsonl[:nblk * DUMP_BLOCK].reshape(nblk, DUMP_BLOCK).sum(
+        axis=1, dtype=np.uint64).astype(np.float64)
+    tail = np.float64(jsonl[nblk * DUMP_BLOCK:].sum(dtype=np.uint64))
+    total += save("jsonl_block_sums", np.append(sums, tail))
+    if nbytes <= DUMP_WINDOWS * DUMP_WINDOW:
+        sample = jsonl
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        starts = np.sort(rng.integers(0, nbytes - DUMP_WINDOW,
+                                      size=DUMP_WINDOWS))
+        sample = np.concatenate([jsonl[s:s + DUMP_WINDOW] for s in starts])
+    total += save("jsonl_sample", sample.astype(np.float32))
+
+    n = last["line_len"].shape[0]
+    rows = rows_of(n, DUMP_MAX_ROWS)
+    total += save("line_off", take(last["line_off"], rows).astype(np.float64))
+    total += save("line_len", take(last["line_len"], rows).astype(np.float32))
+    if "link_cnt" in last:
+        total += save("link_cnt",
+                      take(last["link_cnt"], rows).astype(np.float32))
+        h = take(last["link_hash"], rows_of(n, DUMP_HASH_ROWS))
+        h = np.ascontiguousarray(h).view(np.uint64)
+        total += save("link_hash", np.stack(
+            [(h >> np.uint64(32)).astype(np.float64),
+             (h & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1))
+    total += save("new_discoveries",
+                  np.array([last["new_discoveries"]], dtype=np.float64))
+    assert total <= 64_000_000, f"dump is {total} bytes"
+    log(f"dumped last-step outputs to {dirpath} ({total / 1e6:.1f} MB)")
 
 
 def run_cpu_debug(args):
