@@ -423,6 +423,9 @@ class EncodeResult:
     link_src: torch.Tensor   # uint8[N, MAX_LINKS]
     link_cnt: torch.Tensor   # int32[N]
     link_hash: torch.Tensor  # int64[N, MAX_LINKS] (fnv1a64 bits)
+    writer: str = ""         # staged | plain | lds | scratch ("" = no launch)
+    # test seam: the guarded allocation ``out`` is a view into (_guard > 0)
+    raw: Optional[torch.Tensor] = None
 
 
 def _ptr_array(tensors: List[torch.Tensor]):
@@ -455,12 +458,15 @@ def _stride_bound(batch: B.MessageBatch) -> int:
     ccnt = i64(m["com_cnt"])
     total_c = int(ccnt.sum().item())
     if total_c:
-        cmsg = torch.repeat_interleave(
-            torch.arange(batch.n, dtype=torch.int64, device=dev), ccnt
-        )
+        # segment sums through a prefix array indexed by com_off/com_cnt:
+        # a row subset (select_rows) shares the full comment table, so
+        # the table is not simply the rows' segments laid end to end
         extra = (6 * (i64(batch.com_text_len) + i64(batch.com_handle_len))
                  + 45 * i64(batch.com_react_cnt))
-        bound = bound.index_add(0, cmsg, extra)
+        pre = torch.zeros(extra.numel() + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(extra, 0, out=pre[1:])
+        c0 = i64(m["com_off"])
+        bound = bound + pre[c0 + ccnt] - pre[c0]
     return int(bound.max().item())
 
 
@@ -472,35 +478,96 @@ _EMOJI_POOL_CAP, _EMOJI_CAP, _TS_CAP = 512, 64, 64
 _CTNAME_POOL_CAP, _CTNAME_CAP = 512, 32
 
 
+def _tables_fit(tables, created, capture) -> bool:
+    """True when the per-batch tables fit the staged writer's block caps."""
+    return not (tables["emoji_pool"].numel() > _EMOJI_POOL_CAP
+                or tables["emoji_off"].numel() > _EMOJI_CAP
+                or tables["ctname_pool"].numel() > _CTNAME_POOL_CAP
+                or tables["ctname_off"].numel() > _CTNAME_CAP
+                or len(created) > _TS_CAP or len(capture) > _TS_CAP)
+
+
+def _stage_need(batch) -> int:
+    """Worst-case per-line bytes the staged writer carves from its
+    per-wave LDS stage for this batch (user+title+poster+desc +
+    links/reactions); cached per batch."""
+    need = getattr(batch, "_stage_need", None)
+    if need is None:
+        m = batch.meta
+        need = _STAGE_FIXED
+        if batch.n:
+            need += (max(int(m["text_len"].max().item()),
+                         int(m["aux_len"].max().item()))
+                     + int(m["poster_len"].max().item()))
+        if batch.n_channels:
+            need += (int(batch.ch_user_len.max().item())
+                     + int(batch.ch_title_len.max().item()))
+        try:
+            batch._stage_need = need
+        except AttributeError:
+            pass
+    return need
+
+
+_stage_budget_cache = None
+
+
+def _stage_budget(lib) -> int:
+    global _stage_budget_cache
+    if _stage_budget_cache is None:
+        _stage_budget_cache = int(lib.crawl_stage_budget())
+    return _stage_budget_cache
+
+
 def _stage_fits(batch, lib, tables, created, capture) -> bool:
     """True when every line's staged fields (user+title+poster+desc +
     links/reactions) fit the staged writer's per-wave LDS budget AND
-    the per-batch tables fit its block caps; cached per batch."""
+    the per-batch tables fit its block caps."""
     if os.environ.get("CRAWL_NO_STAGED") == "1":
         return False
-    if (tables["emoji_pool"].numel() > _EMOJI_POOL_CAP
-            or tables["emoji_off"].numel() > _EMOJI_CAP
-            or tables["ctname_pool"].numel() > _CTNAME_POOL_CAP
-            or tables["ctname_off"].numel() > _CTNAME_CAP
-            or len(created) > _TS_CAP or len(capture) > _TS_CAP):
+    if not _tables_fit(tables, created, capture):
         return False
-    fit = getattr(batch, "_stage_fit", None)
-    if fit is None:
-        m = batch.meta
-        mx = _STAGE_FIXED
-        if batch.n:
-            mx += (max(int(m["text_len"].max().item()),
-                       int(m["aux_len"].max().item()))
-                   + int(m["poster_len"].max().item()))
-        if batch.n_channels:
-            mx += (int(batch.ch_user_len.max().item())
-                   + int(batch.ch_title_len.max().item()))
-        fit = mx <= int(lib.crawl_stage_budget())
-        try:
-            batch._stage_fit = fit
-        except AttributeError:
-            pass
-    return fit
+    return _stage_need(batch) <= _stage_budget(lib)
+
+
+def _pick_writer(env, single_pass: bool, stage_need: Optional[int],
+                 budget: int) -> str:
+    """Which JSONL writer parse_encode runs: "scratch" (single-pass
+    scratch + compaction), "lds" (CRAWL_LDS_WRITE set), "staged" (the
+    batch's staged bytes fit the LDS budget) or "plain".
+
+    ``env`` is the environment mapping; ``stage_need`` is
+    :func:`_stage_need` of the batch, or None when the per-batch tables
+    exceed the staged writer's block caps; ``budget`` is
+    crawl_stage_budget()."""
+    if single_pass:
+        return "scratch"
+    if env.get("CRAWL_LDS_WRITE"):
+        return "lds"
+    if env.get("CRAWL_NO_STAGED") == "1":
+        return "plain"
+    if stage_need is not None and stage_need <= budget:
+        return "staged"
+    return "plain"
+
+
+def _alloc_out(total: int, dev, poison: Optional[int], guard: int):
+    """Output allocation: (out, raw). With the test seams off this is a
+    bare torch.empty and raw is None. ``guard`` > 0 places ``out`` inside
+    a larger buffer with ``guard`` poisoned bytes on each side (raw is
+    that buffer); ``poison`` fills the line bytes too, so a writer that
+    skips a byte cannot inherit a stale correct one from the allocator."""
+    if poison is None and guard <= 0:
+        return torch.empty(total, dtype=torch.uint8, device=dev), None
+    guard = max(guard, 0)
+    fill = 0xA5 if poison is None else poison
+    raw = torch.empty(total + 2 * guard, dtype=torch.uint8, device=dev)
+    if poison is not None:
+        raw.fill_(fill)
+    else:
+        raw[:guard].fill_(fill)
+        raw[guard + total:].fill_(fill)
+    return raw[guard:guard + total], raw
 
 
 def parse_encode(
@@ -510,6 +577,9 @@ def parse_encode(
     grid: int = 0,
     stream: Optional[torch.cuda.Stream] = None,
     single_pass: bool = False,
+    *,
+    _poison: Optional[int] = None,
+    _guard: int = 0,
 ) -> EncodeResult:
     """Parse + JSONL-encode a batch on the current CUDA device.
 
@@ -519,11 +589,33 @@ def parse_encode(
     thrashes L2) and is kept for experimentation.
     Returns device tensors; the caller D2H-copies ``out`` for the host
     writer. Byte-for-byte equal to golden_batch.encode_batch(...).
+
+    ``_poison`` / ``_guard`` are test seams (off by default): fill the
+    output (and single-pass scratch) with a byte before the write, and
+    surround ``out`` with that many poisoned bytes (``result.raw``).
     """
     lib = require_lib()
     dev = batch.device
     assert dev.type == "cuda", "parse_encode requires a CUDA (ROCm) batch"
     n = batch.n
+    if n == 0:
+        # nothing to launch: (0 + 3) // 4 blocks is an invalid grid
+        out, raw = _alloc_out(0, dev, _poison, _guard)
+        return EncodeResult(
+            out=out,
+            line_off=torch.zeros(0, dtype=torch.int64, device=dev),
+            line_len=torch.zeros(0, dtype=torch.int32, device=dev),
+            link_name=torch.empty((0, MAX_LINKS, 32), dtype=torch.uint8,
+                                  device=dev),
+            link_len=torch.zeros((0, MAX_LINKS), dtype=torch.uint8,
+                                 device=dev),
+            link_src=torch.zeros((0, MAX_LINKS), dtype=torch.uint8,
+                                 device=dev),
+            link_cnt=torch.zeros(0, dtype=torch.int32, device=dev),
+            link_hash=torch.zeros((0, MAX_LINKS), dtype=torch.int64,
+                                  device=dev),
+            raw=raw,
+        )
     tables = const_tables(dev)
 
     now = now or _dt.datetime.now(_dt.timezone.utc)
@@ -574,9 +666,19 @@ def parse_encode(
         else stream.cuda_stream
     )
 
-    if single_pass:
+    stage_need = None
+    if (not single_pass and not os.environ.get("CRAWL_LDS_WRITE")
+            and os.environ.get("CRAWL_NO_STAGED") != "1"
+            and _tables_fit(tables, created, capture)):
+        stage_need = _stage_need(batch)
+    writer = _pick_writer(os.environ, single_pass, stage_need,
+                          _stage_budget(lib))
+
+    if writer == "scratch":
         stride = (_stride_bound(batch) + 31) & ~15
         scratch = torch.empty(n * stride, dtype=torch.uint8, device=dev)
+        if _poison is not None:
+            scratch.fill_(_poison)
         overflow = torch.zeros(1, dtype=torch.int32, device=dev)
         rc = lib.crawl_write_scratch(
             batch_ptrs, scalars, link_ptrs,
@@ -595,7 +697,7 @@ def parse_encode(
                 f"line overflowed scratch stride ({ovf} > {stride}); "
                 "stride bound is unsound for this batch"
             )
-        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        out, raw = _alloc_out(total, dev, _poison, _guard)
         rc = lib.crawl_compact(
             ctypes.c_void_p(scratch.data_ptr()), stride,
             ctypes.c_void_p(line_off.data_ptr()),
@@ -616,9 +718,8 @@ def parse_encode(
         line_off = torch.zeros(n, dtype=torch.int64, device=dev)
         torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
         total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
-        out = torch.empty(total, dtype=torch.uint8, device=dev)
-        if (not os.environ.get("CRAWL_LDS_WRITE")
-                and _stage_fits(batch, lib, tables, created, capture)):
+        out, raw = _alloc_out(total, dev, _poison, _guard)
+        if writer == "staged":
             # staged writer: escape-scanned fields + reactions +
             # outlinks + per-batch tables go through LDS so in-line
             # loads never wait the store FIFO (profiles/
@@ -634,10 +735,9 @@ def parse_encode(
                 tables["ctname_pool"].numel(), grid, stream_ptr,
             )
         else:
-            writer = (lib.crawl_write_lds
-                      if os.environ.get("CRAWL_LDS_WRITE")
-                      else lib.crawl_write)
-            rc = writer(
+            write_fn = (lib.crawl_write_lds if writer == "lds"
+                        else lib.crawl_write)
+            rc = write_fn(
                 batch_ptrs, scalars, link_ptrs,
                 ctypes.c_void_p(line_off.data_ptr()),
                 ctypes.c_void_p(line_len.data_ptr()),
@@ -649,7 +749,7 @@ def parse_encode(
     return EncodeResult(
         out=out, line_off=line_off, line_len=line_len,
         link_name=link_name, link_len=link_len, link_src=link_src,
-        link_cnt=link_cnt, link_hash=link_hash,
+        link_cnt=link_cnt, link_hash=link_hash, writer=writer, raw=raw,
     )
 
 

@@ -1,0 +1,394 @@
+"""Shared test corpora for the HIP parse+encode writers and the seen-set.
+
+Everything here is CPU-only: builders return packed ``MessageBatch``
+objects (and the python-side inputs they were packed from) so GPU tests
+can run the same batch through every writer, and CPU tests can check the
+corpora's preconditions against the oracle alone.
+"""
+import datetime as dt
+import random
+
+from crawler_amd.ops import batch as B
+from crawler_amd.ops import golden as G
+from crawler_amd.ops.golden_batch import encode_batch
+
+UTC = dt.timezone.utc
+# the one timestamp the new writer/seen-set tests encode with (line
+# lengths depend on it, so builders that target a length use it too)
+NOW = dt.datetime(2026, 3, 4, 5, 6, 7, 890000, tzinfo=UTC)
+
+# ---------------------------------------------------------------- fuzz corpus
+
+WORDS = [
+    "hello", "мир", "data", "🚀", "test", "канал", "🤯", "x" * 40,
+    "a<b", "c&d", "e>f", 'q"r', "s\\t", "line\nbreak", "tab\there",
+    "\u2028sep", "t.me/", "t.me/abcde", "https://t.me/fuzzchan",
+    "@fuzz_name1", "t.me/joinchat/xyz", "plain", "…", "ñé",
+    "t.me/abc", "word_with_underscores_here", "%%", "  ",
+]
+
+
+def rand_text(rng, max_words=14):
+    return " ".join(rng.choice(WORDS) for _ in range(rng.randint(0, max_words)))
+
+
+def utf16_len(s):
+    return sum(2 if ord(c) >= 0x10000 else 1 for c in s)
+
+
+def rand_entities(rng, text):
+    """Well-formed entities at rune boundaries (TDLib guarantees this)."""
+    ents = []
+    if not text or rng.random() < 0.5:
+        return ents
+    for _ in range(rng.randint(1, 3)):
+        # pick a rune-boundary slice
+        i = rng.randint(0, len(text))
+        j = rng.randint(i, min(len(text), i + 20))
+        off16 = utf16_len(text[:i])
+        len16 = utf16_len(text[i:j])
+        etype = rng.choice(["mention", "url", "text_url"])
+        url = ""
+        if etype == "text_url":
+            url = rng.choice([
+                "https://t.me/fuzz_target1", "https://example.com/x",
+                "t.me/abcd", "",
+                # dead t.me before a live one (search must retry)
+                "t.me/ %% t.me/deadlive1",
+                # reserved first match ends the search
+                "t.me/share t.me/after_rsv1",
+            ])
+        # occasionally overshoot the end (golden clamps)
+        if rng.random() < 0.1:
+            len16 += rng.randint(1, 5)
+        ents.append(G.Entity(etype, off16, len16, url=url))
+    return ents
+
+
+def rand_message(rng, k):
+    ct = rng.choice(B.CONTENT_TYPES)
+    text = rand_text(rng)
+    ft = G.FormattedText(text=text, entities=rand_entities(rng, text))
+    reactions = {}
+    for e in rng.sample(B.EMOJI_TABLE, rng.randint(0, 4)):
+        reactions[e] = rng.randint(1, 10_000)
+    return G.SynthMessage(
+        chat_id=-1001000000000 - rng.randint(0, 10**6),
+        msg_id=(k + 1) << 20,
+        date=rng.randint(0, 2_000_000_000),
+        content_type=ct,
+        text=ft if ct == "messageText" else None,
+        caption=ft if ct != "messageText" else None,
+        views=rng.randint(0, 10**9),
+        forwards=rng.randint(0, 10**6),
+        reactions=reactions,
+        media_album_id=rng.choice([0, 0, 0, rng.randint(1, 2**31 - 1)]),
+        thumb_remote_id="AgAD%dt" % (k + 1) if rng.random() < 0.3 else "",
+        video_remote_id="AgAD%dv" % (k + 1) if rng.random() < 0.2 else "",
+        document_name=rand_text(rng, 2) if ct == "messageDocument" else "",
+        emoji="🎉" if ct == "messageAnimatedEmoji" else "",
+        poll_question=rand_text(rng, 3) if ct == "messagePoll" else "",
+        giveaway_prize="premium" if ct == "messageGiveaway" else "",
+        poster_handle=rng.choice(["", "user123", "фантом", 'we"ird\\']),
+    )
+
+
+def rand_comments(rng, n_msgs):
+    out = []
+    for _ in range(n_msgs):
+        coms = []
+        if rng.random() < 0.3:
+            for _ in range(rng.randint(1, 3)):
+                reacts = {}
+                for e in rng.sample(B.EMOJI_TABLE, rng.randint(0, 2)):
+                    reacts[e] = rng.randint(1, 500)
+                coms.append((rand_text(rng, 5),
+                             rng.choice(["u1", "коммент", ""]),
+                             rng.randint(0, 10**6), rng.randint(0, 999),
+                             reacts))
+        out.append(coms)
+    return out
+
+
+def fuzz_corpus(seed, n):
+    """(msgs, batch): n random messages with comments over 4 channels."""
+    rng = random.Random(seed)
+    msgs = [rand_message(rng, k) for k in range(n)]
+    # reply_count must match packed comments for golden comment fetch
+    comments = rand_comments(rng, n)
+    for m, c in zip(msgs, comments):
+        m.reply_count = len(c)
+    channels = [B.ChannelRow(
+        chat_id=-1001, username="fuzzchan%03d" % i,
+        title=rand_text(rng, 3) or "t", member_count=rng.randint(0, 10**6),
+        post_count=rng.randint(0, 10**5), total_views=rng.randint(0, 10**9),
+    ) for i in range(4)]
+    chan_of = [rng.randrange(4) for _ in range(n)]
+    batch = B.pack(msgs, channels, chan_of, comments_of_msg=comments)
+    return msgs, batch
+
+
+def fuzz_batch(seed, n=120):
+    """The fuzz corpus with comments and 4 channels."""
+    return fuzz_corpus(seed, n)[1]
+
+
+def median_cutoff(batch):
+    """min_post_date at the batch's median date: filtered and kept lines
+    interleave (dates are random per row)."""
+    dates = sorted(int(d) for d in batch.meta["date"])
+    return dt.datetime.fromtimestamp(dates[len(dates) // 2], UTC)
+
+
+def future_cutoff(batch):
+    """A min_post_date above every date in the batch."""
+    return dt.datetime.fromtimestamp(
+        max(int(d) for d in batch.meta["date"]) + 1, UTC)
+
+
+# ------------------------------------------------------ handcrafted edge cases
+
+EDGE_TEXTS = [
+    # overlap/cursor semantics
+    "t.me/abcdet.me/xyz12 tail",
+    # 32-char cap
+    "t.me/" + "a" + "b" * 40,
+    # reserved + valid
+    "t.me/joinchat/xx t.me/okchan1",
+    # https prefix + dup
+    "https://t.me/dupdup1 t.me/dupdup1",
+    # unicode + escapes + U+2028
+    'привет "мир" <>&\n\u2028 t.me/unichan1 🚀',
+    # no links
+    "just plain text",
+    # mention entity with cyrillic prefix
+    "канал @mention_chan тут",
+]
+
+
+def edge_batch():
+    """(texts, batch): adversarial messages through the real packer."""
+    msgs = []
+    texts = list(EDGE_TEXTS)
+    for k, t in enumerate(texts):
+        ents = []
+        if "@mention_chan" in t:
+            off = t.index("@")
+            ents.append(G.Entity("mention", off, len("@mention_chan")))
+        msgs.append(G.SynthMessage(
+            chat_id=-100123, msg_id=(k + 1) << 20, date=1_700_000_000 + k,
+            content_type="messageText",
+            text=G.FormattedText(text=t, entities=ents),
+            views=k * 10, forwards=k, reactions={"👍": k + 1},
+            poster_handle=f"user{k:04d}",
+        ))
+    ch = [B.ChannelRow(chat_id=-100123, username="edgechan1",
+                       title='Edge "Chan" <&>', member_count=5,
+                       post_count=len(msgs), total_views=100)]
+    return texts, B.pack(msgs, ch, [0] * len(msgs))
+
+
+# ------------------------------------------------ SWAR block-boundary escapes
+
+def swar_texts():
+    """Adversarial placement of escape bytes around the measure pass's
+    256-byte SWAR blocks (common.h esc fast path): U+2028/29 leaders at
+    block edges, specials at every lane-word position, long clean runs."""
+    U2028 = "\u2028"
+    U2029 = "\u2029"
+    texts = []
+    # E2-leader at byte offsets straddling the 256-byte block boundary.
+    # description starts at the raw text start, so byte index within the
+    # field == byte index within the python string's utf-8 encoding.
+    for lead in (253, 254, 255, 256, 257):
+        t = "a" * lead + U2028 + "b" * 300
+        texts.append(t)
+        texts.append("a" * lead + U2029 + "b" * 300)
+    # special byte at each position of the first lane word
+    for pos in (0, 1, 2, 3, 63, 64, 127, 255, 256, 511):
+        t = ("x" * pos) + '"' + ("y" * 400)
+        texts.append(t)
+    # a control byte deep in an otherwise clean 1KB run
+    texts.append("c" * 700 + "\x07" + "d" * 300)
+    # fully clean 1KB (pure fast path), clean multiple-of-256
+    texts.append("e" * 1024)
+    texts.append("f" * 512)
+    # dirty first block then long clean tail (fast path must re-engage)
+    texts.append("<&>" + "g" * 900)
+    # non-ascii high bytes that are NOT E2 sequences (must stay clean-ish)
+    texts.append("п" * 400)   # 0xD0 0xBF pairs
+    # E2 that is NOT a U+2028/29 (e.g. '…' U+2026 = E2 80 A6)
+    texts.append("h" * 250 + "…" + "i" * 300)
+    return texts
+
+
+def swar_batch():
+    """(texts, batch) for :func:`swar_texts`."""
+    texts = swar_texts()
+    msgs = []
+    for k, t in enumerate(texts):
+        msgs.append(G.SynthMessage(
+            chat_id=-100555, msg_id=(k + 1) << 20,
+            date=1_700_100_000 + k, content_type="messageText",
+            text=G.FormattedText(text=t),
+            views=k, forwards=0, poster_handle=f"user{k:04d}",
+        ))
+    ch = [B.ChannelRow(chat_id=-100555, username="swarchan1",
+                       title="SWAR", member_count=3,
+                       post_count=len(msgs), total_views=9)]
+    return texts, B.pack(msgs, ch, [0] * len(msgs))
+
+
+# ------------------------------------------------------------- LDS ladder
+
+LDS_LINE_BYTES = 3072   # parse_encode.hip: write_lds_kernel's per-wave buffer
+_ESC_UNIT = '"<\n\u2028'    # 6 raw bytes -> 16 escaped bytes
+
+
+def _ladder_pack(texts):
+    msgs = [G.SynthMessage(
+        chat_id=-100888, msg_id=(k + 1) << 20, date=1_700_200_000 + k,
+        content_type="messageText", text=G.FormattedText(text=t),
+        views=100 + k, forwards=k % 7, poster_handle="poster%02d" % (k % 100),
+    ) for k, t in enumerate(texts)]
+    ch = [B.ChannelRow(chat_id=-100888, username="ldsladder", title="L",
+                       member_count=7, post_count=len(msgs), total_views=70)]
+    return B.pack(msgs, ch, [0] * len(msgs))
+
+
+# target oracle line length per row (None = text given verbatim)
+_LADDER_PLAN = [
+    (40, None), (3070, None), (41, None), (3071, None), (42, None),
+    (3072, None), (43, None), (3073, None), (3074, None),
+    # cross LDS_LINE_BYTES only after escaping
+    (None, _ESC_UNIT * 100),
+    (None, "a" * 700 + _ESC_UNIT * 40 + "tail"),
+    (44, None), (3072, None), (3071, None), (3070, None),
+]
+
+
+def lds_ladder():
+    """One batch of clean-ASCII messageText posts whose oracle line
+    lengths cover 3070..3074 (straddling ``LDS_LINE_BYTES``), two lines
+    that exceed it only after escaping, and line starts in all four
+    residues mod 4 (the funnel-shift copy's head/tail cases).
+
+    Text lengths are derived from the oracle: a probe batch with 1-byte
+    texts gives each row's fixed overhead (clean ASCII adds one output
+    byte per text byte)."""
+    probe = _ladder_pack(["x" if t is None else t for _, t in _LADDER_PLAN])
+    base, _ = encode_batch(probe, now=NOW)
+    texts = []
+    for (target, text), line in zip(_LADDER_PLAN, base):
+        if text is not None:
+            texts.append(text)
+        elif target < 1000:          # short filler: text length as given
+            texts.append("s" * target)
+        else:
+            texts.append("k" * (target - (len(line) - 1)))
+    return _ladder_pack(texts)
+
+
+def lds_ladder_escape_rows():
+    """Row indices of the two escape-crossing lines in lds_ladder()."""
+    return [i for i, (_, t) in enumerate(_LADDER_PLAN) if t is not None]
+
+
+# ----------------------------------------------------------- stage ladder
+
+_STAGE_USER = "stage_chan_01"
+_STAGE_TITLE = 'Stage "T" <&>\n\u2028я'
+_STAGE_POSTER = 'we"ird\\'
+
+
+def _stage_text(nbytes):
+    """Exactly ``nbytes`` UTF-8 bytes: 8 distinct valid t.me links, some
+    escapes and multi-byte runes, then clean ASCII padding."""
+    head = " ".join("t.me/stagelink%02d" % j for j in range(8))
+    head += ' я"<\n\u2028> 🚀 '
+    pad = nbytes - len(head.encode("utf-8"))
+    assert pad >= 0, "stage budget too small for the link header"
+    return head + "p" * pad
+
+
+def _stage_batch(field_bytes):
+    long_text = _stage_text(field_bytes)
+    doc_name = 'doc "n" <&> ' + "d" * (field_bytes - 12)
+    msgs = [
+        G.SynthMessage(
+            chat_id=-100999, msg_id=1 << 20, date=1_700_300_000,
+            content_type="messageText",
+            text=G.FormattedText(text=long_text),
+            views=12345, forwards=67,
+            reactions={e: 10 + j for j, e in enumerate(B.EMOJI_TABLE)},
+            poster_handle=_STAGE_POSTER,
+        ),
+        G.SynthMessage(
+            chat_id=-100999, msg_id=2 << 20, date=1_700_300_001,
+            content_type="messageDocument",
+            caption=G.FormattedText(text="see t.me/stagedoc01"),
+            document_name=doc_name, views=5, forwards=1,
+            reactions={"🔥": 3}, poster_handle=_STAGE_POSTER,
+        ),
+        G.SynthMessage(
+            chat_id=-100999, msg_id=3 << 20, date=1_700_300_002,
+            content_type="messageText",
+            text=G.FormattedText(text="short t.me/stageshort1"),
+            views=1, forwards=0, poster_handle="u3",
+        ),
+    ]
+    ch = [B.ChannelRow(chat_id=-100999, username=_STAGE_USER,
+                       title=_STAGE_TITLE, member_count=11,
+                       post_count=len(msgs), total_views=999)]
+    return B.pack(msgs, ch, [0] * len(msgs))
+
+
+def stage_ladder(budget, fixed):
+    """(at, over): two batches whose staged-writer gate arithmetic
+    ``fixed + max(text, aux) + poster + user + title`` lands exactly on
+    ``budget`` and on ``budget + 1``. Row 0 carries 8 distinct links and
+    all 10 reactions at the maximum text length; row 1 takes its
+    description from ``aux`` (a document name) at the same length."""
+    rest = (len(_STAGE_POSTER.encode("utf-8"))
+            + len(_STAGE_USER.encode("utf-8"))
+            + len(_STAGE_TITLE.encode("utf-8")))
+    field = budget - fixed - rest
+    return _stage_batch(field), _stage_batch(field + 1)
+
+
+# --------------------------------------------------------- seen-set hashes
+
+_U64 = (1 << 64) - 1
+
+
+def home_slot_hashes(home, count, slots_log2, salt=0):
+    """``count`` distinct 64-bit hashes whose home slot (h & (slots-1))
+    is ``home``; high bits are scrambled so some have the top bit set."""
+    mask = (1 << slots_log2) - 1
+    out = []
+    for j in range(count):
+        hi = ((j + 1 + salt) * 0x9E3779B97F4A7C15) & _U64 & ~mask
+        out.append(hi | home)
+    return out
+
+
+def wrap_chain_hashes():
+    """40 hashes homed at the last slot of a 64-slot table (the probe
+    sequence must wrap to slot 0) plus 8 homed at slot 0 (pushed along
+    by the wrapped chain)."""
+    return home_slot_hashes(63, 40, 6), home_slot_hashes(0, 8, 6, salt=1000)
+
+
+def bloom_hashes():
+    """Two claim rounds for the bloom check: includes h = 0, hashes with
+    the top bit set, and a pair sharing their low bloom probe."""
+    first = [0, 1 << 63, _U64, 0x8000000000000401, 0x0000000100000401,
+             0x123456789ABCDEF0, 0xFEDCBA9876543210, 5, 1023 | (1023 << 32)]
+    second = [0x0F0F0F0F0F0F0F0F, 0x8000000000000000 | 777, 5,
+              0x00000200_00000100]
+    return first, second
+
+
+def dup_hashes():
+    """16 distinct hashes, to be tiled over 2048 link slots."""
+    return [((j + 1) * 0xD6E8FEB86659FD93) & _U64 | 2 for j in range(16)]

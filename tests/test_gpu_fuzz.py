@@ -5,111 +5,18 @@ well-formed entities, random reactions/comments, random t.me material)
 through the real packer and asserts byte-identical JSONL + identical
 link sets. Deterministic seeds so failures reproduce."""
 import datetime as dt
-import random
+import os
 
 import pytest
 import torch
 
-from crawler_amd.ops import batch as B
-from crawler_amd.ops import golden as G
 from crawler_amd.ops.golden_batch import encode_batch
+
+from _corpora import fuzz_corpus
 
 pytestmark = pytest.mark.gpu
 
 NOW = dt.datetime(2026, 5, 6, 7, 8, 9, tzinfo=dt.timezone.utc)
-
-WORDS = [
-    "hello", "мир", "data", "🚀", "test", "канал", "🤯", "x" * 40,
-    "a<b", "c&d", "e>f", 'q"r', "s\\t", "line\nbreak", "tab\there",
-    " sep", "t.me/", "t.me/abcde", "https://t.me/fuzzchan",
-    "@fuzz_name1", "t.me/joinchat/xyz", "plain", "…", "ñé",
-    "t.me/abc", "word_with_underscores_here", "%%", "  ",
-]
-
-
-def rand_text(rng, max_words=14):
-    return " ".join(rng.choice(WORDS) for _ in range(rng.randint(0, max_words)))
-
-
-def utf16_len(s):
-    return sum(2 if ord(c) >= 0x10000 else 1 for c in s)
-
-
-def rand_entities(rng, text):
-    """Well-formed entities at rune boundaries (TDLib guarantees this)."""
-    ents = []
-    if not text or rng.random() < 0.5:
-        return ents
-    for _ in range(rng.randint(1, 3)):
-        # pick a rune-boundary slice
-        i = rng.randint(0, len(text))
-        j = rng.randint(i, min(len(text), i + 20))
-        off16 = utf16_len(text[:i])
-        len16 = utf16_len(text[i:j])
-        etype = rng.choice(["mention", "url", "text_url"])
-        url = ""
-        if etype == "text_url":
-            url = rng.choice([
-                "https://t.me/fuzz_target1", "https://example.com/x",
-                "t.me/abcd", "",
-                # dead t.me before a live one (search must retry)
-                "t.me/ %% t.me/deadlive1",
-                # reserved first match ends the search
-                "t.me/share t.me/after_rsv1",
-            ])
-        # occasionally overshoot the end (golden clamps)
-        if rng.random() < 0.1:
-            len16 += rng.randint(1, 5)
-        ents.append(G.Entity(etype, off16, len16, url=url))
-    return ents
-
-
-def rand_message(rng, k):
-    ct = rng.choice(B.CONTENT_TYPES)
-    text = rand_text(rng)
-    ft = G.FormattedText(text=text, entities=rand_entities(rng, text))
-    reactions = {}
-    for e in rng.sample(B.EMOJI_TABLE, rng.randint(0, 4)):
-        reactions[e] = rng.randint(1, 10_000)
-    return G.SynthMessage(
-        chat_id=-1001000000000 - rng.randint(0, 10**6),
-        msg_id=(k + 1) << 20,
-        date=rng.randint(0, 2_000_000_000),
-        content_type=ct,
-        text=ft if ct == "messageText" else None,
-        caption=ft if ct != "messageText" else None,
-        views=rng.randint(0, 10**9),
-        forwards=rng.randint(0, 10**6),
-        reactions=reactions,
-        media_album_id=rng.choice([0, 0, 0, rng.randint(1, 2**31 - 1)]),
-        thumb_remote_id="AgAD%dt" % (k + 1) if rng.random() < 0.3 else "",
-        video_remote_id="AgAD%dv" % (k + 1) if rng.random() < 0.2 else "",
-        document_name=rand_text(rng, 2) if ct == "messageDocument" else "",
-        emoji="🎉" if ct == "messageAnimatedEmoji" else "",
-        poll_question=rand_text(rng, 3) if ct == "messagePoll" else "",
-        giveaway_prize="premium" if ct == "messageGiveaway" else "",
-        poster_handle=rng.choice(["", "user123", "фантом", 'we"ird\\']),
-    )
-
-
-def rand_comments(rng, n_msgs):
-    out = []
-    for _ in range(n_msgs):
-        coms = []
-        if rng.random() < 0.3:
-            for _ in range(rng.randint(1, 3)):
-                reacts = {}
-                for e in rng.sample(B.EMOJI_TABLE, rng.randint(0, 2)):
-                    reacts[e] = rng.randint(1, 500)
-                coms.append((rand_text(rng, 5),
-                             rng.choice(["u1", "коммент", ""]),
-                             rng.randint(0, 10**6), rng.randint(0, 999),
-                             reacts))
-        out.append(coms)
-    return out
-
-
-import os
 
 _SEEDS = [11, 22, 33]
 if os.environ.get("CRAWL_FUZZ_SEEDS"):
@@ -121,21 +28,7 @@ if os.environ.get("CRAWL_FUZZ_SEEDS"):
 def test_fuzz_batches_byte_identical(seed):
     from crawler_amd.ops import gpu
 
-    rng = random.Random(seed)
-    n = 300
-    msgs = [rand_message(rng, k) for k in range(n)]
-    # reply_count must match packed comments for golden comment fetch
-    comments = rand_comments(rng, n)
-    for m, c in zip(msgs, comments):
-        m.reply_count = len(c)
-    channels = [B.ChannelRow(
-        chat_id=-1001, username="fuzzchan%03d" % i,
-        title=rand_text(rng, 3) or "t", member_count=rng.randint(0, 10**6),
-        post_count=rng.randint(0, 10**5), total_views=rng.randint(0, 10**9),
-    ) for i in range(4)]
-    chan_of = [rng.randrange(4) for _ in range(n)]
-    batch = B.pack(msgs, channels, chan_of, comments_of_msg=comments)
-
+    msgs, batch = fuzz_corpus(seed, 300)
     golden_lines, golden_links = encode_batch(batch, now=NOW)
     res = gpu.parse_encode(batch.to("cuda:0"), now=NOW)
     torch.cuda.synchronize()

@@ -15,6 +15,8 @@ from crawler_amd.ops import batch as B
 from crawler_amd.ops import golden as G
 from crawler_amd.ops.golden_batch import encode_batch
 
+from _corpora import edge_batch, swar_batch
+
 pytestmark = pytest.mark.gpu
 
 UTC = dt.timezone.utc
@@ -98,39 +100,7 @@ def test_min_post_date_filter(gpu_mod, feed):
 
 def test_handcrafted_edge_cases(gpu_mod):
     """Pack adversarial messages through the real packer and compare."""
-    msgs = []
-    texts = [
-        # overlap/cursor semantics
-        "t.me/abcdet.me/xyz12 tail",
-        # 32-char cap
-        "t.me/" + "a" + "b" * 40,
-        # reserved + valid
-        "t.me/joinchat/xx t.me/okchan1",
-        # https prefix + dup
-        "https://t.me/dupdup1 t.me/dupdup1",
-        # unicode + escapes + U+2028
-        'привет "мир" <>&\n  t.me/unichan1 🚀',
-        # no links
-        "just plain text",
-        # mention entity with cyrillic prefix
-        "канал @mention_chan тут",
-    ]
-    for k, t in enumerate(texts):
-        ents = []
-        if "@mention_chan" in t:
-            off = t.index("@")
-            ents.append(G.Entity("mention", off, len("@mention_chan")))
-        msgs.append(G.SynthMessage(
-            chat_id=-100123, msg_id=(k + 1) << 20, date=1_700_000_000 + k,
-            content_type="messageText",
-            text=G.FormattedText(text=t, entities=ents),
-            views=k * 10, forwards=k, reactions={"👍": k + 1},
-            poster_handle=f"user{k:04d}",
-        ))
-    ch = [B.ChannelRow(chat_id=-100123, username="edgechan1",
-                       title='Edge "Chan" <&>', member_count=5,
-                       post_count=len(msgs), total_views=100)]
-    batch = B.pack(msgs, ch, [0] * len(msgs))
+    texts, batch = edge_batch()
     from crawler_amd.ops import gpu
 
     golden_lines, golden_links = encode_batch(batch, now=NOW)
@@ -159,44 +129,7 @@ def test_swar_block_boundary_escapes(gpu_mod):
     """Adversarial placement of escape bytes around the measure pass's
     256-byte SWAR blocks (common.h esc fast path): U+2028/29 leaders at
     block edges, specials at every lane-word position, long clean runs."""
-    U2028 = " "
-    U2029 = " "
-    texts = []
-    # E2-leader at byte offsets straddling the 256-byte block boundary.
-    # description starts at the raw text start, so byte index within the
-    # field == byte index within the python string's utf-8 encoding.
-    for lead in (253, 254, 255, 256, 257):
-        t = "a" * lead + U2028 + "b" * 300
-        texts.append(t)
-        texts.append("a" * lead + U2029 + "b" * 300)
-    # special byte at each position of the first lane word
-    for pos in (0, 1, 2, 3, 63, 64, 127, 255, 256, 511):
-        t = ("x" * pos) + '"' + ("y" * 400)
-        texts.append(t)
-    # a control byte deep in an otherwise clean 1KB run
-    texts.append("c" * 700 + "\x07" + "d" * 300)
-    # fully clean 1KB (pure fast path), clean multiple-of-256
-    texts.append("e" * 1024)
-    texts.append("f" * 512)
-    # dirty first block then long clean tail (fast path must re-engage)
-    texts.append("<&>" + "g" * 900)
-    # non-ascii high bytes that are NOT E2 sequences (must stay clean-ish)
-    texts.append("п" * 400)   # 0xD0 0xBF pairs
-    # E2 that is NOT a U+2028/29 (e.g. '…' U+2026 = E2 80 A6)
-    texts.append("h" * 250 + "…" + "i" * 300)
-
-    msgs = []
-    for k, t in enumerate(texts):
-        msgs.append(G.SynthMessage(
-            chat_id=-100555, msg_id=(k + 1) << 20,
-            date=1_700_100_000 + k, content_type="messageText",
-            text=G.FormattedText(text=t),
-            views=k, forwards=0, poster_handle=f"user{k:04d}",
-        ))
-    ch = [B.ChannelRow(chat_id=-100555, username="swarchan1",
-                       title="SWAR", member_count=3,
-                       post_count=len(msgs), total_views=9)]
-    batch = B.pack(msgs, ch, [0] * len(msgs))
+    texts, batch = swar_batch()
     from crawler_amd.ops import gpu
 
     golden_lines, _ = encode_batch(batch, now=NOW)
