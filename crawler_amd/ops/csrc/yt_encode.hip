@@ -48,55 +48,86 @@ struct YtView {
   int n;
 };
 
-#define YT_MAX_URLS 8
-
+// A URL ends at the reference's byte-level whitespace (Go RE2 \S in
+// urlPattern, youtube_crawler.go:61: [\t\n\f\r ]) plus this project's
+// deliberate < > ". \v, the other control bytes, 0x7F and every
+// non-ASCII byte continue a URL. Oracle: convert._URL_RE.
 DEV bool url_stop_char(unsigned char c) {
-  return c <= ' ' || c == '<' || c == '>' || c == '"';
+  // one bit per stop byte (all below 64): this test runs once per URL byte
+  const unsigned long long stops =
+      (1ULL << ' ') | (1ULL << '\t') | (1ULL << '\n') | (1ULL << '\f') |
+      (1ULL << '\r') | (1ULL << '<') | (1ULL << '>') | (1ULL << '"');
+  return c < 64 && ((stops >> c) & 1ULL);
 }
 DEV bool url_trim_char(unsigned char c) {
   return c == ',' || c == '.' || c == ';' || c == ':' || c == '!' ||
          c == '?' || c == '(' || c == ')' || c == '\'' || c == '"';
 }
 
-// Extract up to YT_MAX_URLS http(s) URLs from text; stores (start,len)
-// pairs referencing the text itself (no per-thread URL buffers -> no
-// scratch spill). Oracle: convert.extract_urls.
-DEV int extract_urls(const unsigned char* s, int n, int* starts,
-                     int* lens) {
-  int cnt = 0;
-  int p = 0;
-  while (p + 7 <= n && cnt < YT_MAX_URLS) {
-    bool http = s[p] == 'h' && s[p + 1] == 't' && s[p + 2] == 't' &&
-                s[p + 3] == 'p';
-    if (!http) { ++p; continue; }
-    int q = p + 4;
-    if (q < n && s[q] == 's') ++q;
-    if (!(q + 2 < n && s[q] == ':' && s[q + 1] == '/' && s[q + 2] == '/')) {
-      ++p;
-      continue;
-    }
-    int end = p;
-    while (end < n && !url_stop_char(s[end])) ++end;
-    int e2 = end;
-    while (e2 > p && url_trim_char(s[e2 - 1])) --e2;
-    int len = e2 - p;
-    if (len > 0) {
-      bool dup = false;
-      for (int k = 0; k < cnt && !dup; ++k) {
-        if (lens[k] != len) continue;
-        bool eq = true;
-        for (int j = 0; j < len; ++j) eq &= (s[starts[k] + j] == s[p + j]);
-        dup = eq;
+// Iterator over the http(s) URL matches of text s[0..n), in order, with
+// trailing punctuation trimmed (oracle: convert.extract_urls before its
+// dedup). A match is "http://" or "https://" plus AT LEAST ONE non-stop
+// byte, and runs to the next stop byte; it yields (start, len) into the
+// text itself. Nothing is stored per URL, so any number of URLs costs no
+// registers or scratch. Never reads at or past s[n].
+struct UrlScan {
+  const unsigned char* s;
+  int n;
+  int p;      // scan position
+  int start;  // last match
+  int len;
+  int last;   // its final byte, s[start + len - 1]
+
+  DEV bool next() {
+    while (p + 8 <= n) {  // shortest match: "http://x"
+      bool http = s[p] == 'h' && s[p + 1] == 't' && s[p + 2] == 't' &&
+                  s[p + 3] == 'p';
+      if (!http) { ++p; continue; }
+      int q = p + 4;
+      if (s[q] == 's') ++q;
+      if (!(q + 3 < n && s[q] == ':' && s[q + 1] == '/' &&
+            s[q + 2] == '/' && !url_stop_char(s[q + 3]))) {
+        ++p;
+        continue;
       }
-      if (!dup) {
-        starts[cnt] = p;
-        lens[cnt] = len;
-        ++cnt;
-      }
+      int end = q + 4;
+      while (end < n && !url_stop_char(s[end])) ++end;
+      int e2 = end;  // '/' is no trim byte: e2 stays past the "//"
+      unsigned char c = s[e2 - 1];
+      while (url_trim_char(c)) c = s[--e2 - 1];
+      start = p;
+      len = e2 - p;
+      last = c;
+      p = end;
+      return true;
     }
-    p = end > p ? end : p + 1;
+    return false;
   }
-  return cnt;
+};
+
+// True when the URL (start, len) already occurred as a match that
+// begins in [from, start). Dedup re-scans instead of remembering URLs:
+// quadratic in the URL count of one description, which the API caps at
+// 5000 bytes. The caller skips the re-scan for a URL whose url_key() no
+// earlier URL had.
+DEV bool url_seen_before(const unsigned char* s, int n, int from,
+                         int start, int len) {
+  UrlScan r{s, n, from, 0, 0, 0};
+  while (r.next() && r.start < start) {
+    if (r.len != len) continue;
+    int j = 0;
+    while (j < len && s[r.start + j] == s[start + j]) ++j;
+    if (j == len) return true;
+  }
+  return false;
+}
+
+// One of 64 filter bits from a URL's length and final byte, both known
+// when the scan returns it. Equal URLs have equal keys, so a URL whose
+// bit no earlier URL of the description set is new without a re-scan
+// (the usual case: a few URLs of different lengths).
+DEV unsigned long long url_key(const UrlScan& u) {
+  return 1ULL << ((u.len + 5 * u.last) & 63);
 }
 
 // YEmit extends the shared JsonEmit (common.h) with the sanitized
@@ -149,10 +180,6 @@ DEV int emit_yt(const YtView& B, int i, unsigned char* out) {
   const int comments = B.comments[i];
   const long long engagement =
       (long long)likes + comments + views / 100;
-
-  int url_starts[YT_MAX_URLS];
-  int url_lens[YT_MAX_URLS];
-  const int n_urls = extract_urls(desc, desc_n, url_starts, url_lens);
 
   auto video_url = [&]() {
     LIT(e, "https://www.youtube.com/watch?v=");
@@ -233,6 +260,8 @@ DEV int emit_yt(const YtView& B, int i, unsigned char* out) {
   e.i64(likes);
   LIT(e, ",\"shares\":null,\"comments\":");
   e.i64(comments);
+  // a float64 in the reference and the oracle: views is valid in
+  // 0 .. 2^53 (YouTubeBatch), where the integer prints the same
   LIT(e, ",\"views\":");
   e.i64(views);
   LIT(e, "},\"has_embed_media\":true,\"description\":\"");
@@ -263,10 +292,21 @@ DEV int emit_yt(const YtView& B, int i, unsigned char* out) {
   e.raw(vid, 11);
   LIT(e, "/hq.jpg\",\"media_url\":\"\",\"comments\":null,"
          "\"reactions\":null,\"outlinks\":[");
-  for (int k = 0; k < n_urls; ++k) {
-    if (k) LIT(e, ",");
+  // every distinct URL of the description, in first-appearance order
+  // (oracle: convert.extract_urls)
+  UrlScan u{desc, desc_n, 0, 0, 0, 0};
+  unsigned long long url_keys = 0;  // url_key() of every URL so far
+  int first_url = 0;
+  while (u.next()) {
+    const unsigned long long key = url_key(u);
+    if ((url_keys & key) &&
+        url_seen_before(desc, desc_n, first_url, u.start, u.len))
+      continue;
+    if (url_keys) LIT(e, ",");
+    else first_url = u.start;
+    url_keys |= key;
     LIT(e, "\"");
-    e.esc(desc + url_starts[k], url_lens[k]);
+    e.esc(desc + u.start, u.len);
     LIT(e, "\"");
   }
   LIT(e, "],\"capture_time\":\"");

@@ -136,15 +136,38 @@ _YT_PTR_ORDER = [
 ]
 
 
+class YtEncodeResult(tuple):
+    """``(out, line_off, line_len)`` of yt_parse_encode. ``raw`` is the
+    guarded allocation ``out`` is a view into (test seam ``_guard`` > 0),
+    else None."""
+
+    raw: Optional[torch.Tensor] = None
+
+    def __new__(cls, out, line_off, line_len, raw=None):
+        self = super().__new__(cls, (out, line_off, line_len))
+        self.raw = raw
+        return self
+
+
 def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
-                    grid: int = 0) -> Tuple[torch.Tensor, torch.Tensor,
-                                            torch.Tensor]:
+                    grid: int = 0, *, _poison: Optional[int] = None,
+                    _guard: int = 0) -> Tuple[torch.Tensor, torch.Tensor,
+                                              torch.Tensor]:
     """YouTube batch -> (out bytes, line_off, line_len); byte-identical to
-    youtube.batch.encode_yt_batch."""
+    youtube.batch.encode_yt_batch.
+
+    ``_poison`` / ``_guard`` are the test seams of :func:`parse_encode`
+    (off by default): the guarded buffer is the result's ``.raw``."""
     lib = require_lib()
     dev = batch.device
     assert dev.type == "cuda"
     n = batch.n
+    if n == 0:
+        # nothing to launch: (0 + 3) // 4 blocks is an invalid grid
+        out, raw = _alloc_out(0, dev, _poison, _guard)
+        return YtEncodeResult(
+            out, torch.zeros(0, dtype=torch.int64, device=dev),
+            torch.zeros(0, dtype=torch.int32, device=dev), raw)
     now = now or _dt.datetime.now(_dt.timezone.utc)
     created = format_go_time(now.replace(microsecond=0)).encode()
     capture = format_go_time(now).encode()
@@ -173,16 +196,15 @@ def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
         raise RuntimeError(f"crawl_yt_measure failed: hip {rc}")
     line_off = torch.zeros(n, dtype=torch.int64, device=dev)
     torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
-    total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
-    out = torch.empty(total, dtype=torch.uint8, device=dev)
+    total = int(line_off[-1].item() + line_len[-1].item())
+    out, raw = _alloc_out(total, dev, _poison, _guard)
     rc = lib.crawl_yt_write(ptrs, scalars,
                             ctypes.c_void_p(line_off.data_ptr()),
                             ctypes.c_void_p(out.data_ptr()),
                             grid, stream_ptr)
     if rc != 0:
         raise RuntimeError(f"crawl_yt_write failed: hip {rc}")
-    return out, line_off, line_len
-
+    return YtEncodeResult(out, line_off, line_len, raw)
 
 
 

@@ -23,6 +23,14 @@ UTC = _dt.timezone.utc
 
 @dataclasses.dataclass
 class YouTubeBatch:
+    """SoA video rows + channel table over one byte pool.
+
+    Domain: ``views`` is valid in ``0 .. 2**53``. performance_scores.views
+    is a float64 in the reference and in the oracle, and the device
+    encoder prints the integer; the two agree exactly on that range and
+    neither is required to be right above it. Dates (``published``,
+    ``ch_published``) are valid for years 1 to 9999."""
+
     n: int
     vid_off: torch.Tensor       # int32[N] -> pool (11 bytes each)
     channel_idx: torch.Tensor   # int32[N]
@@ -163,9 +171,10 @@ def pack_videos(videos: List[YouTubeVideo],
 
 
 def build_corpus(index: SyntheticYouTubeIndex, n_videos: int,
-                 crawl_label: str = "") -> YouTubeBatch:
+                 crawl_label: str = "", i0: int = 0) -> YouTubeBatch:
     """Deterministic corpus: sequential samplable video ids + their
-    channels (host-side; setup cost only)."""
+    channels (host-side; setup cost only). ``i0`` is the index of the
+    first video (the prefix walk wraps at 26**5)."""
     import string
 
     videos: List[YouTubeVideo] = []
@@ -173,7 +182,7 @@ def build_corpus(index: SyntheticYouTubeIndex, n_videos: int,
     chan_pos = {}
     channel_of: List[int] = []
     k = 0
-    i = 0
+    i = i0
     while len(videos) < n_videos:
         # deterministic prefix walk over aaaaa..zzzzz space
         p = ""
@@ -301,13 +310,13 @@ def _cid_bytes_vec(index: SyntheticYouTubeIndex,
 
 
 def build_corpus_fast(index: SyntheticYouTubeIndex, n_videos: int,
-                      crawl_label: str = "") -> YouTubeBatch:
+                      crawl_label: str = "", i0: int = 0) -> YouTubeBatch:
     """Vectorized build_corpus: byte-identical encode output (pinned by
     tests/test_youtube.py::test_build_corpus_fast_matches_slow), ~20x
     faster (the python path costs ~140 us/video; 1.2M-video bench
     corpora took minutes of setup)."""
     n = n_videos
-    i_arr = np.arange(n, dtype=np.uint64)
+    i_arr = np.arange(i0, i0 + n, dtype=np.uint64)
 
     # prefix chars: 5-digit base-26 of i, MSB first (build_corpus walk)
     pchars = np.empty((n, 5), dtype=np.uint64)

@@ -31,7 +31,14 @@ _ISO_DUR = re.compile(
     r"^P(?:(?P<days>\d+)D)?(?:T(?:(?P<hours>\d+)H)?(?:(?P<minutes>\d+)M)?"
     r"(?:(?P<seconds>\d+)S)?)?$"
 )
-_URL_RE = re.compile(r"https?://[^\s<>\"]+")
+# A URL ends at the reference's byte-level whitespace: Go RE2 `\S+` in
+# urlPattern (youtube_crawler.go:61) stops at [\t\n\f\r ] only, so \v, the
+# other control bytes, 0x7F and every non-ASCII character (U+00A0, U+2028,
+# ...) continue a URL. Also stopping at < > " is this project's deliberate
+# deviation from the reference (markup around a link is not part of it).
+# The device scanner (ops/csrc/yt_encode.hip url_stop_char) uses the same
+# set on UTF-8 bytes.
+_URL_RE = re.compile(r"https?://[^\t\n\f\r <>\"]+")
 _SANITIZE_RE = re.compile(r"[^A-Za-z0-9._-]+")
 
 

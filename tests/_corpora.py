@@ -392,3 +392,288 @@ def bloom_hashes():
 def dup_hashes():
     """16 distinct hashes, to be tiled over 2048 link slots."""
     return [((j + 1) * 0xD6E8FEB86659FD93) & _U64 | 2 for j in range(16)]
+
+
+# ------------------------------------------------------- YouTube encoder
+#
+# Hand-made rows for csrc/yt_encode.hip, packed with pack_videos; one
+# small generator per concern. Every string is valid UTF-8 (the oracle
+# decodes strictly) and none holds byte 0xA5, the poison the GPU tests
+# pre-fill the output with. pack_videos lays the pool out as
+# [id | title | description] per row, then the channel table, so row
+# i's description is followed directly by row i+1's 11-byte id.
+
+YT_POISON = 0xA5
+YT_MAX_VIEWS = 2 ** 53      # YouTubeBatch: views is valid in 0 .. 2**53
+_YT_EPOCH = dt.datetime(1970, 1, 1, tzinfo=UTC)
+
+
+def _yt_time(secs):
+    return _YT_EPOCH + dt.timedelta(seconds=secs)
+
+
+def _yt_video(k, title="t", desc="", vid=None, published=None, views=0,
+              likes=0, comments=0, duration="PT1M1S", language="en"):
+    from crawler_amd.youtube.synth import YouTubeVideo
+
+    return YouTubeVideo(
+        id=vid or "v%04d-abcde" % k, channel_id="", title=title,
+        description=desc,
+        published_at=_yt_time(1_700_000_000 + k if published is None
+                              else published),
+        view_count=views, like_count=likes, comment_count=comments,
+        duration=duration, language=language)
+
+
+def _yt_channel(k, title=None, desc="about", country="US", subs=0,
+                videos=0, views=0, published=1_600_000_000):
+    from crawler_amd.youtube.synth import YouTubeChannel
+
+    return YouTubeChannel(
+        id="UC%022d" % k, title="Chan %d" % k if title is None else title,
+        description=desc, subscriber_count=subs, video_count=videos,
+        view_count=views, country=country, published_at=_yt_time(published))
+
+
+def _yt_pack(videos, channels=None, channel_of=None, label="yt-matrix"):
+    from crawler_amd.youtube.batch import pack_videos
+
+    if channels is None:
+        channels, channel_of = [_yt_channel(0)], [0] * len(videos)
+    return pack_videos(videos, channels, channel_of, crawl_label=label)
+
+
+def _yt_many_urls(count, tag):
+    return " ".join("https://m%s.example/p%02d" % (tag, j)
+                    for j in range(count))
+
+
+_YT_TRIM = ",.;:!?()'\""
+_YT_STOPS = "\t\n\f\r <>\""
+
+# (description, id of the row or None). pack_videos puts row i+1's id
+# right behind row i's description, so an id is the bait a scanner that
+# reads past desc_len would pick up.
+_YT_URL_ROWS = [
+    # bare scheme: before a space, before '<', at end of text
+    ("see http:// x", None),
+    ("http://<b", None),
+    ("https:// and https://<b> and https://\"q\"", None),
+    ("bare at end http://", None),
+    ("plain text", "x.example/y"),       # would complete the bare scheme
+    ("bare at end https://", None),
+    ("both http://a.example/1 https://b.example/2", None),
+    ("HTTP://a Http://b hTTps://c", None),
+    ("hthttp://a", None),
+    ("httphttp://a", None),
+    ("httpshttps://a httpss://b http:/c http//d", None),
+    ("http://a<http://b", None),
+    ("https://a.b/c).,", None),
+    ("(https://a.b/d?!;:')", None),
+    ("http://.", None),
+    ("http://.,; https://:", None),
+    # every trim byte alone ('"' also stops the URL)
+    (" ".join("x https://t%d.example/c%s y" % (j, c)
+              for j, c in enumerate(_YT_TRIM)), None),
+    # duplicates that differ only by trimmed punctuation
+    ("http://dup.example/x, http://dup.example/x. (http://dup.example/x)"
+     " http://dup.example/x", None),
+    # equal length, last byte differs; then a true duplicate of the first
+    ("http://same.len/a http://same.len/b http://same.len/a"
+     " http://same.len/c http://same.len/b", None),
+    # bytes that CONTINUE a URL under the byte-level stop set
+    ("http://a\x01b c", None),
+    ("http://a\x0bb c", None),
+    ("http://a\x7fb c", None),
+    ("http://a\u00a0b c", None),
+    ("http://a\u2028b c", None),
+    ("http://a\x1cb\x1d\x1e\x1f\u0085\u3000c d", None),
+    # each real stop byte
+    (" ".join("http://s%d%stop" % (j, c)
+              for j, c in enumerate(_YT_STOPS)), None),
+    # a URL that needs JSON escaping
+    ("https://e.sc/?a=1&b=2\\c&d https://e.sc/?a=1&b=2\\c&d.", None),
+    (_yt_many_urls(9, "a"), None),
+    (_yt_many_urls(10, "b"), None),
+    (_yt_many_urls(40, "c"), None),
+    # 12 URLs of which 4 repeat earlier ones
+    (" ".join(["https://d.example/%d" % j for j in range(8)]
+              + ["https://d.example/3,", "https://d.example/0",
+                 "https://d.example/7.", "https://d.example/5"]), None),
+    # 12 URLs, 9 distinct: a repeat of the 9th, and of the 1st after it
+    (" ".join(["https://g.example/%d" % j for j in range(9)]
+              + ["https://g.example/8", "https://g.example/0.",
+                 "https://g.example/8,"]), None),
+    # shorter than the shortest match, and empty
+    ("http:/", None),
+    ("h", None),
+    ("", None),
+    # a URL ending exactly at desc_len, the next row's id continuing it
+    ("end http://tail.example/p", None),
+    ("after the bait", "ath/http://"),
+    # "htt" at the very end, the next row's id completing the scheme
+    ("see htt", None),
+    ("after the second bait", "p://abc.de/"),
+    # equal length AND equal last byte, different in the middle; then
+    # true duplicates of both
+    ("http://mid.a/x http://mid.b/x, http://mid.a/x http://mid.b/x", None),
+]
+
+
+def yt_url_edges():
+    """Descriptions for the URL scanner: bare schemes, scheme
+    look-alikes, trimming, dedup, the byte-level stop set, more than 8
+    URLs, escapes, and text cut off by desc_len with URL-like bytes
+    right behind it."""
+    return _yt_pack([_yt_video(k, title="url %d" % k, desc=d, vid=vid)
+                     for k, (d, vid) in enumerate(_YT_URL_ROWS)])
+
+
+def yt_sanitize_edges():
+    """Titles for sanitized(): run collapsing and the 80-byte cap."""
+    titles = [
+        "", "!!!", "!", "  lead", "trail  ", "in  ner   runs",
+        "\u00e9\u00e9\u00e9", "a\U0001F680b",
+        "\u00e9\u00e9\u00e9\U0001F680\u00e9x\u00e9", "keep.dots-and_under",
+        "..--__", "s" * 79 + "!!y", "s" * 79 + "y", "s" * 79 + "!",
+        "s" * 80 + "more", "s" * 80 + "!!", "s" * 80, "a!" * 60,
+        "!a" * 60, "!" * 200 + "x", "\u00e9" * 200 + "x",
+        "w" * 78 + "\U0001F680\U0001F680zz",
+    ]
+    return _yt_pack([_yt_video(k, title=t, desc="d%d" % k)
+                     for k, t in enumerate(titles)])
+
+
+YT_ESC_LENGTHS = [0, 1, 3, 4, 5, 63, 64, 65, 255, 256, 257, 259, 260,
+                  511, 512, 513, 1030]
+_YT_SPECIALS = ['"', "\\", "\n", "<", "&", "\x01"]
+
+
+def _yt_esc_strings():
+    """The ladder's strings: each length clean, then with ONE special
+    byte at the first, the last, and every 256-byte block-boundary-1 /
+    block-boundary position below the length. The special cycles through
+    the six escape classes from string to string; at length 513 all six
+    sit at both sides of the first block boundary. Then U+2028 at every
+    split over a block start, and an E2-led non-2028 character there."""
+    out = []
+    k = 0
+    for n in YT_ESC_LENGTHS:
+        out.append("a" * n)
+        pos = {0, n - 1} | {b + d for b in range(256, n + 1, 256)
+                            for d in (-1, 0)}
+        for p in sorted(q for q in pos if 0 <= q < n):
+            sp = _YT_SPECIALS[k % 6]
+            k += 1
+            out.append("b" * p + sp + "c" * (n - p - 1))
+    for sp in _YT_SPECIALS:
+        for p in (255, 256):
+            out.append("d" * p + sp + "e" * (513 - p - 1))
+    for lead in (253, 254, 255, 256, 509, 510, 511, 512):
+        out.append("f" * lead + "\u2028" + "g" * 300)
+    for lead in (253, 254, 255, 256):
+        out.append("h" * lead + "\u2014" + "i" * 300)
+    return out + swar_texts()
+
+
+def _yt_esc_batch(strings, label):
+    """Row i: title strings[i], description strings[i+1]; one channel
+    per 4 rows carrying three more of them (title, description,
+    country)."""
+    m = len(strings)
+    videos = [_yt_video(k, title=strings[k], desc=strings[(k + 1) % m])
+              for k in range(m)]
+    channels = [_yt_channel(j, title=strings[(4 * j) % m],
+                            desc=strings[(4 * j + 1) % m],
+                            country=strings[(4 * j + 2) % m])
+                for j in range((m + 3) // 4)]
+    return _yt_pack(videos, channels, [k // 4 for k in range(m)], label)
+
+
+YT_LABELS = ["", 'la"b\\el <&>\n\u2028\u00e9',
+             "l" * 255 + '"' + "m" * 44]
+
+
+def yt_esc_ladder():
+    """List of batches (<= 40 rows each) over :func:`_yt_esc_strings`,
+    the same strings in title, description, channel title, channel
+    description and country; then one small batch per crawl_label in
+    YT_LABELS (empty, escaped, 300 bytes)."""
+    strings = _yt_esc_strings()
+    out = [_yt_esc_batch(strings[i:i + 40], "esc-%d" % i)
+           for i in range(0, len(strings), 40)]
+    few = ["plain", 'q"<\n', "n" * 300]
+    out += [_yt_esc_batch(few, label) for label in YT_LABELS]
+    return out
+
+
+_YT_BIG = sorted({0, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1}
+                 | {10 ** k - d for k in range(1, 16) for d in (0, 1)})
+YT_DATES = [-62135596800, -1, 0, 951782400, 4107542400, 68169600,
+            253402300799]
+_YT_DURATIONS = ["P0D", "PT0S", "PT1S", "PT%dS" % (2 ** 31 - 1)]
+_I32_MAX = 2 ** 31 - 1
+
+
+def yt_number_edges():
+    """Counters at every decimal-length step and around 2**32 (the
+    32/64-bit split of u64()), the int32 and int64 maxima, engagement
+    past int32, durations and dates at the edges of their domains."""
+    views = _YT_BIG + [2 ** 53 - 1, 2 ** 53]
+    ch_big = _YT_BIG + [2 ** 63 - 1]
+    videos, channels = [], []
+    for k, v in enumerate(views):
+        likes = _I32_MAX if k % 3 == 0 else 0
+        comments = _I32_MAX if k % 3 != 1 else 0   # k % 3 == 0: both max
+        videos.append(_yt_video(
+            k, views=v, likes=likes, comments=comments,
+            duration=_YT_DURATIONS[k % 4], language=("en", "ru")[k % 2],
+            published=YT_DATES[k % 7], title="n%d" % k, desc="v=%d" % v))
+    for j, s in enumerate(ch_big):
+        channels.append(_yt_channel(
+            j, subs=s, views=ch_big[(j + 5) % len(ch_big)],
+            videos=_I32_MAX if j % 2 else 0,
+            published=YT_DATES[(j + 3) % 7]))
+    return _yt_pack(videos, channels,
+                    [k % len(channels) for k in range(len(videos))])
+
+
+YT_SHAPE_NS = [1, 2, 3, 5, 7, 9]
+
+
+def yt_shape_batches():
+    """{n: batch} for n in YT_SHAPE_NS: the first n of nine rows whose
+    line lengths differ widely; rows share channels, and the channel
+    table's order is not the rows' first-appearance order."""
+    descs = ["", "http://s.example/1 " * 30, "short", "x" * 900 + "<&>",
+             _yt_many_urls(12, "s"), "d", "\u2028" * 90, "e" * 257,
+             "last http://s.example/z."]
+    titles = ["t", "T" * 300, "", "a!" * 50, "mid", "\u00e9" * 120,
+              "t6", "s" * 81, "nine"]
+    channel_of = [3, 0, 3, 1, 0, 2, 3, 1, 0]
+    channels = [_yt_channel(j, title="C%d " % j + "z" * (70 * j),
+                            desc="about " * (5 * (3 - j)),
+                            country=("US", "", "DE", "")[j], subs=10 ** j)
+                for j in range(4)]
+    videos = [_yt_video(k, title=titles[k], desc=descs[k], views=7 ** k,
+                        likes=k, comments=2 * k) for k in range(9)]
+    return {n: _yt_pack(videos[:n], channels, channel_of[:n])
+            for n in YT_SHAPE_NS}
+
+
+def yt_corpora():
+    """{name: batch}: every YouTube corpus above, one entry per batch."""
+    out = {"url": yt_url_edges(), "sanitize": yt_sanitize_edges(),
+           "numbers": yt_number_edges()}
+    for j, b in enumerate(yt_esc_ladder()):
+        out["esc%d" % j] = b
+    for n, b in yt_shape_batches().items():
+        out["shape%d" % n] = b
+    return out
+
+
+def encode_yt_lines(batch):
+    """Oracle lines of a YouTube batch at NOW."""
+    from crawler_amd.youtube.batch import encode_yt_batch
+
+    return encode_yt_batch(batch, now=NOW)
