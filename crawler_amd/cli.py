@@ -97,6 +97,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--synthetic-posts", type=int, default=1000)
     a("--disable-rate-limits", action="store_true")
     a("--pool-size", type=int, default=2)
+    a("--yt-max-searches", type=int, default=200,
+      help="youtube random sampling: upper bound on prefix searches")
+    a("--yt-daily-quota", type=int, default=10_000,
+      help="youtube: API quota units available to the crawl")
     return p
 
 
@@ -161,6 +165,8 @@ def parse_config(argv: Optional[List[str]] = None) -> CrawlerConfig:
         youtube_api_key=args.youtube_api_key,
         synthetic_seed=args.synthetic_seed,
         disable_rate_limits=args.disable_rate_limits,
+        yt_max_searches=args.yt_max_searches,
+        yt_daily_quota=args.yt_daily_quota,
     )
     if args.min_post_date:
         import datetime as dt

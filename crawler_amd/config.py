@@ -97,6 +97,8 @@ class CrawlerConfig:
     device_batch_posts: int = 1 << 20   # posts per GPU parse batch
     synthetic_seed: int = 1234          # RNG seed for the synthetic feed
     disable_rate_limits: bool = False   # neutralize pacing for benchmarks
+    yt_max_searches: int = 200          # GetRandomVideos search bound
+    yt_daily_quota: int = 10_000        # YouTube API units per day
 
     # Runtime-injected (not a flag)
     null_validator: object = None

@@ -12,8 +12,8 @@ import sys
 
 CSRC = os.path.dirname(os.path.abspath(__file__)) + "/csrc"
 SOURCES = ["parse_encode.hip", "dedup.hip", "feedgen.hip", "yt_encode.hip",
-           "yt_feedgen.hip", "aggregate.hip", "htmlclass.hip",
-           "sample.hip"]
+           "yt_feedgen.hip", "yt_sample.hip", "aggregate.hip",
+           "htmlclass.hip", "sample.hip"]
 OUT = os.path.join(CSRC, "libcrawlhip.so")
 
 
@@ -22,7 +22,7 @@ def needs_build() -> bool:
         return True
     out_m = os.path.getmtime(OUT)
     deps = [os.path.join(CSRC, s) for s in SOURCES]
-    deps += [os.path.join(CSRC, "common.h")]
+    deps += [os.path.join(CSRC, h) for h in ("common.h", "yt_hash.h")]
     return any(os.path.getmtime(d) > out_m for d in deps)
 
 

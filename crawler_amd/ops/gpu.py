@@ -75,6 +75,7 @@ def load_lib():
     _bind_feedgen(lib)
     _bind_v2(lib)
     _bind_yt(lib)
+    _bind_yt_sample(lib)
     _bind_aux(lib)
     _lib = lib
     return lib
@@ -206,6 +207,186 @@ def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
         raise RuntimeError(f"crawl_yt_write failed: hip {rc}")
     return YtEncodeResult(out, line_off, line_len, raw)
 
+
+
+# ---------- YouTube sampling (csrc/yt_sample.hip) ----------
+
+YT_SEARCH_SLOTS = 17   # n_valid <= 5, n_noise <= 12
+YT_UPLOAD_SLOTS = 29   # video_count <= 29
+
+
+def _bind_yt_sample(lib):
+    vp, ll, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
+    sigs = {
+        "crawl_yt_search": [ll, ll, vp, ll] + [vp] * 5 + [vp],
+        "crawl_yt_claim_insert": [vp, vp, vp, ll, ll, vp, vp, ci, vp, vp],
+        "crawl_yt_first_claim": [vp, vp, ll, ll, vp, vp, ci, vp, vp, vp],
+        "crawl_yt_uploads": [ll, vp, ll, ci, vp, vp, vp],
+        "crawl_yt_gen_meta_ids": [ll] * 4 + [vp] * 11 + [vp],
+        "crawl_yt_gen_fill_ids": [ll] * 3 + [vp] * 6 + [vp],
+        "crawl_yt_chan_lens": [ll, vp, ll, vp, vp, vp, vp],
+    }
+    for name, argtypes in sigs.items():
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = argtypes
+
+
+def _cur_stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _vp(t: Optional[torch.Tensor]):
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
+
+
+def yt_search(index, prefixes: torch.Tensor) -> dict:
+    """SyntheticYouTubeIndex.search_prefix + the client's validity rule
+    for ``prefixes`` (uint8[S,5] on the device). Returns per-slot
+    tensors over S*17 slots: ``ids`` uint8[S,17,11], ``flags`` uint8[S,17]
+    (bit 0 present, bit 1 rule-valid), and for rule-valid slots ``keys``
+    (exact 64-bit id key), ``chan`` (channel index) and ``vcount`` (that
+    channel's video_count)."""
+    lib = require_lib()
+    dev = prefixes.device
+    assert dev.type == "cuda" and prefixes.dtype == torch.uint8
+    prefixes = prefixes.reshape(-1, 5).contiguous()
+    S = prefixes.shape[0]
+    m = S * YT_SEARCH_SLOTS
+    out = {
+        "ids": torch.empty((S, YT_SEARCH_SLOTS, 11), dtype=torch.uint8,
+                           device=dev),
+        "flags": torch.empty((S, YT_SEARCH_SLOTS), dtype=torch.uint8,
+                             device=dev),
+        "keys": torch.empty(m, dtype=torch.int64, device=dev),
+        "chan": torch.empty(m, dtype=torch.int64, device=dev),
+        "vcount": torch.empty(m, dtype=torch.int32, device=dev),
+    }
+    rc = lib.crawl_yt_search(
+        index.seed, index.universe, _vp(prefixes), S, _vp(out["ids"]),
+        _vp(out["flags"]), _vp(out["keys"]), _vp(out["chan"]),
+        _vp(out["vcount"]), _cur_stream())
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_search failed: hip {rc}")
+    return out
+
+
+def yt_uploads(index, chans: torch.Tensor, limit: int):
+    """SyntheticYouTubeIndex.channel_uploads for channel indices
+    ``chans`` (int64[K] on the device): (ids uint8[K,29,11], counts
+    int32[K]); slot k of row c is an upload iff k < counts[c]."""
+    lib = require_lib()
+    dev = chans.device
+    assert dev.type == "cuda" and chans.dtype == torch.int64
+    chans = chans.contiguous()
+    K = chans.numel()
+    ids = torch.empty((K, YT_UPLOAD_SLOTS, 11), dtype=torch.uint8,
+                      device=dev)
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    limit = max(0, min(int(limit), YT_UPLOAD_SLOTS))
+    rc = lib.crawl_yt_uploads(index.seed, _vp(chans), K, limit, _vp(ids),
+                              _vp(counts), _cur_stream())
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_uploads failed: hip {rc}")
+    return ids, counts
+
+
+class YtClaimTableError(RuntimeError):
+    """The first-claim table's device error word was set: a probe wrapped
+    the whole table (full), or a key equalled the empty sentinel."""
+
+
+class YtFirstClaim:
+    """Deterministic first-occurrence marking over 64-bit keys.
+
+    An open-addressing table in HBM (keys + min global index). ``claim``
+    returns, for each masked-in element, whether it is the first
+    occurrence of its key over every claim so far; elements are numbered
+    by the caller's global index (``base_idx + i``), so the answer does
+    not depend on thread scheduling. The table grows by doubling to keep
+    the load <= 0.5 (``grow=False`` pins its size: a full table raises
+    :class:`YtClaimTableError`)."""
+
+    _EMPTY = -1  # all-ones; real keys are < 2**63
+
+    def __init__(self, device, slots_log2: int = 16, grow: bool = True):
+        self.device = torch.device(device)
+        self.grow = grow
+        self.grown = 0
+        self._lib = require_lib()
+        self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._alloc(slots_log2)
+        self._bound = 0  # upper bound on the distinct keys held
+
+    def _alloc(self, slots_log2: int):
+        self.slots_log2 = slots_log2
+        cap = 1 << slots_log2
+        self.keys = torch.full((cap,), self._EMPTY, dtype=torch.int64,
+                               device=self.device)
+        self.min_idx = torch.full((cap,), -1, dtype=torch.int64,
+                                  device=self.device)
+
+    def _check(self):
+        e = int(self._err.item())
+        if e:
+            self._err.zero_()
+            raise YtClaimTableError(
+                f"first-claim table error word {e:#x} "
+                f"(slots=2**{self.slots_log2})")
+
+    def _reserve(self, incoming: int):
+        if not self.grow:
+            return
+        cap = 1 << self.slots_log2
+        if 2 * (self._bound + incoming) <= cap:
+            return
+        # recount exactly, then double until the load fits; re-insert
+        # the retained (key, first index) pairs with the pass-1 kernel
+        live = self.keys != self._EMPTY
+        old_k = self.keys[live].contiguous()
+        old_i = self.min_idx[live].contiguous()
+        self._bound = int(old_k.numel())
+        log2 = self.slots_log2
+        while 2 * (self._bound + incoming) > (1 << log2):
+            log2 += 1
+            self.grown += 1
+        if log2 == self.slots_log2:
+            return
+        self._alloc(log2)
+        rc = self._lib.crawl_yt_claim_insert(
+            _vp(old_k), None, _vp(old_i), old_k.numel(), 0,
+            _vp(self.keys), _vp(self.min_idx), self.slots_log2,
+            _vp(self._err), _cur_stream())
+        if rc != 0:
+            raise RuntimeError(f"crawl_yt_claim_insert failed: hip {rc}")
+        self._check()
+
+    def claim(self, keys: torch.Tensor, mask: Optional[torch.Tensor],
+              base_idx: int) -> torch.Tensor:
+        """keys int64[n]; mask uint8[n]/bool[n] or None (all in).
+        Returns uint8[n]: 1 = first occurrence."""
+        assert keys.dtype == torch.int64 and keys.device == self.device
+        keys = keys.contiguous()
+        n = keys.numel()
+        first = torch.zeros(n, dtype=torch.uint8, device=self.device)
+        if n == 0:
+            return first
+        if mask is not None:
+            mask = mask.to(torch.uint8).contiguous()
+            assert mask.numel() == n
+            incoming = int(mask.count_nonzero().item())
+        else:
+            incoming = n
+        self._reserve(incoming)
+        rc = self._lib.crawl_yt_first_claim(
+            _vp(keys), _vp(mask), n, int(base_idx), _vp(self.keys),
+            _vp(self.min_idx), self.slots_log2, _vp(first),
+            _vp(self._err), _cur_stream())
+        if rc != 0:
+            raise RuntimeError(f"crawl_yt_first_claim failed: hip {rc}")
+        self._bound += incoming
+        self._check()
+        return first
 
 
 def _bind_aux(lib):

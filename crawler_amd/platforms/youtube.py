@@ -17,6 +17,17 @@ class YouTubeCrawler(PlatformCrawler):
     def run(self, ctx: CrawlContext) -> dict:
         from ..youtube.runner import run_youtube
 
+        if getattr(ctx.args, "gpu", False):
+            if ctx.cfg.sampling_method in ("random", "channel"):
+                from ..youtube.gpu_runner import run_youtube_gpu
+
+                stats = run_youtube_gpu(ctx.cfg, ctx.urls)
+                print(f"youtube gpu crawl complete: {stats}",
+                      file=sys.stderr)
+                return stats
+            print("youtube: the GPU mode covers random and channel "
+                  "sampling; running snowball on the CPU",
+                  file=sys.stderr)
         stats = run_youtube(ctx.cfg, ctx.urls)
         print(f"youtube crawl complete: {stats}", file=sys.stderr)
         return stats

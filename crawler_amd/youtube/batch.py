@@ -592,3 +592,127 @@ def build_corpus_device(index: SyntheticYouTubeIndex, n_videos: int,
         ch_published=ch_published,
         crawl_label=crawl_label,
     )
+
+
+def yt_meta_from_ids_device(index: SyntheticYouTubeIndex,
+                            ids_u8: torch.Tensor) -> dict:
+    """Per-video numeric fields for an id array (uint8[n,11] on the
+    device): everything ``index.video(id)`` derives from the id's
+    ``vidmeta`` hash. ``n_chan`` is the channel index."""
+    from ..ops import gpu as _g
+
+    lib = _g.require_lib()
+    dev = ids_u8.device
+    assert dev.type == "cuda" and ids_u8.dtype == torch.uint8
+    vid_pool = ids_u8.reshape(-1, 11).contiguous()
+    n = vid_pool.shape[0]
+    e = lambda dt_: torch.empty(n, dtype=dt_, device=dev)
+    m = {"vid_pool": vid_pool, "published": e(torch.int64),
+         "views": e(torch.int64), "likes": e(torch.int32),
+         "comments": e(torch.int32), "duration_s": e(torch.int32),
+         "lang": e(torch.int32), "n_chan": e(torch.int64),
+         "topic": e(torch.int32), "tnum": e(torch.int32),
+         "desc_len": e(torch.int32)}
+    p = _g._vp
+    rc = lib.crawl_yt_gen_meta_ids(
+        index.seed, index.universe, index.base_date, n, p(vid_pool),
+        p(m["published"]), p(m["views"]), p(m["likes"]), p(m["comments"]),
+        p(m["duration_s"]), p(m["lang"]), p(m["n_chan"]), p(m["topic"]),
+        p(m["tnum"]), p(m["desc_len"]), _g._cur_stream())
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_gen_meta_ids failed: hip {rc}")
+    return m
+
+
+def build_batch_from_ids_device(index: SyntheticYouTubeIndex,
+                                ids_u8: torch.Tensor, device,
+                                crawl_label: str = "") -> YouTubeBatch:
+    """Device batch for the videos NAMED by ``ids_u8`` (uint8[n,11]):
+    the id-driven sibling of :func:`build_corpus_device`, for search
+    hits and channel uploads. Equal, through the encoder, to
+    ``pack_videos([index.video(id) ...])`` with a first-appearance
+    channel table. Unlike build_corpus_device the channel table's string
+    lengths come from a kernel, so nothing returns to the host but the
+    two pool-size scalars. Callers keep n <= 1M so the int32 pool
+    offsets hold."""
+    from ..ops import gpu as _g
+
+    lib = _g.require_lib()
+    dev = torch.device(device)
+    ids_u8 = ids_u8.to(dev)
+    m = yt_meta_from_ids_device(index, ids_u8)
+    vid_pool, desc_len, n_chan = m["vid_pool"], m["desc_len"], m["n_chan"]
+    n = vid_pool.shape[0]
+    p, stream = _g._vp, _g._cur_stream()
+    ar = torch.arange(n, dtype=torch.int64, device=dev)
+
+    # layout: [vid n*11 | title n*27 | desc var | channel region]
+    vid_off = ar * 11
+    title_off = n * 11 + ar * 27
+    desc_base = n * 11 + n * 27
+    dl64 = desc_len.to(torch.int64)
+    desc_off = torch.cumsum(dl64, 0) - dl64 + desc_base
+    desc_total = int(desc_base + dl64.sum().item())
+
+    # channel table in FIRST-APPEARANCE order
+    uniq, inverse = torch.unique(n_chan, sorted=True, return_inverse=True)
+    K = uniq.numel()
+    first = torch.full((K,), n, dtype=torch.int64, device=dev)
+    first.scatter_reduce_(0, inverse, ar, reduce="amin")
+    order = torch.argsort(first)
+    rank = torch.empty_like(order)
+    rank[order] = torch.arange(K, dtype=torch.int64, device=dev)
+    channel_idx = rank[inverse].to(torch.int32)
+    chan_ns = uniq[order].contiguous()
+
+    title_len_ch = torch.empty(K, dtype=torch.int64, device=dev)
+    desc_len_ch = torch.empty(K, dtype=torch.int64, device=dev)
+    country_len = torch.empty(K, dtype=torch.int64, device=dev)
+    rc = lib.crawl_yt_chan_lens(index.seed, p(chan_ns), K,
+                                p(title_len_ch), p(desc_len_ch),
+                                p(country_len), stream)
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_chan_lens failed: hip {rc}")
+    block = 24 + title_len_ch + desc_len_ch + country_len
+    id_off = torch.cumsum(block, 0) - block + desc_total
+    t_off = id_off + 24
+    d_off = t_off + title_len_ch
+    c_off = d_off + desc_len_ch
+    total = int(desc_total + block.sum().item())
+    if total >= 2 ** 31:
+        raise ValueError(
+            f"batch pool of {total} bytes overflows the int32 offsets; "
+            "chunk the ids")
+
+    pool = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+    rc = lib.crawl_yt_gen_fill_ids(
+        index.seed, index.universe, n, p(vid_pool), p(m["topic"]),
+        p(m["tnum"]), p(title_off), p(desc_off), p(pool), stream)
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_gen_fill_ids failed: hip {rc}")
+    z = lambda dt_: torch.empty(K, dtype=dt_, device=dev)
+    subs, videos_t = z(torch.int64), z(torch.int32)
+    ch_views, ch_published = z(torch.int64), z(torch.int64)
+    if K:
+        rc = lib.crawl_yt_gen_channels(
+            index.seed, index.universe, index.base_date, p(chan_ns), K,
+            p(id_off), p(t_off), p(d_off), p(c_off), p(subs),
+            p(videos_t), p(ch_views), p(ch_published), p(pool), stream)
+        if rc != 0:
+            raise RuntimeError(f"crawl_yt_gen_channels failed: hip {rc}")
+
+    i32 = lambda t_: t_.to(torch.int32)
+    return YouTubeBatch(
+        n=n, vid_off=i32(vid_off), channel_idx=channel_idx,
+        published=m["published"], views=m["views"], likes=m["likes"],
+        comments=m["comments"], duration_s=m["duration_s"],
+        lang=m["lang"], title_off=title_off,
+        title_len=torch.full((n,), 27, dtype=torch.int32, device=dev),
+        desc_off=desc_off, desc_len=desc_len, pool=pool,
+        n_channels=int(K), ch_id_off=i32(id_off), ch_title_off=i32(t_off),
+        ch_title_len=i32(title_len_ch), ch_desc_off=i32(d_off),
+        ch_desc_len=i32(desc_len_ch), ch_subs=subs, ch_videos=videos_t,
+        ch_views=ch_views, ch_published=ch_published,
+        ch_country_off=i32(c_off), ch_country_len=i32(country_len),
+        crawl_label=crawl_label,
+    )

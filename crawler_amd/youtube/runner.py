@@ -11,7 +11,7 @@ import random
 from typing import List
 
 from ..engine.state import LocalStateManager
-from .client import QuotaExceeded, SyntheticYouTubeClient
+from .client import QUOTA_DAILY, QuotaExceeded, SyntheticYouTubeClient
 from .convert import convert_video_to_post
 from .synth import SyntheticYouTubeIndex
 
@@ -21,6 +21,7 @@ def run_youtube(cfg, urls: List[str], client=None, sm=None,
     """Dispatch by cfg.sampling_method: channel | random | snowball."""
     client = client or SyntheticYouTubeClient(
         SyntheticYouTubeIndex(seed=getattr(cfg, "synthetic_seed", 99)),
+        daily_quota=getattr(cfg, "yt_daily_quota", QUOTA_DAILY),
         min_channel_videos=cfg.min_channel_videos,
         rng=random.Random(getattr(cfg, "synthetic_seed", 99)),
     )
@@ -28,7 +29,8 @@ def run_youtube(cfg, urls: List[str], client=None, sm=None,
     limit = limit or (cfg.max_posts if cfg.max_posts > 0 else 100)
 
     if cfg.sampling_method == "random":
-        videos = client.get_random_videos(limit)
+        videos = client.get_random_videos(
+            limit, max_searches=getattr(cfg, "yt_max_searches", 200))
     elif cfg.sampling_method == "snowball":
         seeds = [u for u in urls]
         # seed "urls" may be channel indices or UC ids; resolve indices
