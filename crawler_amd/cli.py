@@ -101,6 +101,8 @@ def build_parser() -> argparse.ArgumentParser:
       help="youtube random sampling: upper bound on prefix searches")
     a("--yt-daily-quota", type=int, default=10_000,
       help="youtube: API quota units available to the crawl")
+    a("--yt-gpu-snowball", action="store_true",
+      help="youtube: with --gpu, run snowball sampling on the GPU too")
     return p
 
 

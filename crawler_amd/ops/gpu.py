@@ -225,6 +225,11 @@ def _bind_yt_sample(lib):
         "crawl_yt_gen_meta_ids": [ll] * 4 + [vp] * 11 + [vp],
         "crawl_yt_gen_fill_ids": [ll] * 3 + [vp] * 6 + [vp],
         "crawl_yt_chan_lens": [ll, vp, ll, vp, vp, vp, vp],
+        # csrc/yt_snowball.hip
+        "crawl_yt_scan_count": [vp, vp, vp, ll, vp, vp],
+        "crawl_yt_scan_write": [vp, vp, vp, ll, vp, vp, vp],
+        "crawl_yt_cid_table_build": [ll, ll, vp, ci, vp, vp],
+        "crawl_yt_cid_lookup": [ll, vp, vp, ll, vp, ci, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)
@@ -387,6 +392,119 @@ class YtFirstClaim:
         self._bound += incoming
         self._check()
         return first
+
+
+# ---------- YouTube snowball discovery (csrc/yt_snowball.hip) ----------
+
+YT_CID_LEN = 24   # 'UC' + 22 characters
+
+
+def yt_scan_channel_ids(pool: torch.Tensor, text_off: torch.Tensor,
+                        text_len: torch.Tensor):
+    """Leftmost non-overlapping matches of ``UC[0-9A-Za-z_-]{22}`` in the
+    texts ``pool[text_off[t] : text_off[t] + text_len[t]]`` (uint8 pool,
+    int64[n] offsets, int32[n] lengths, all on the device): the bytes
+    regex's ``finditer`` starts. Returns ``(hit_off int64[m], counts
+    int32[n])``: every match's absolute pool offset, in text order then
+    match order, and the per-text match count. A match lies wholly inside
+    its text; texts may be packed back to back."""
+    lib = require_lib()
+    dev = pool.device
+    assert dev.type == "cuda" and pool.dtype == torch.uint8
+    assert text_off.dtype == torch.int64 and text_len.dtype == torch.int32
+    assert text_off.device == dev and text_len.device == dev
+    pool = pool.contiguous()
+    text_off = text_off.contiguous()
+    text_len = text_len.contiguous()
+    n = text_off.numel()
+    assert text_len.numel() == n
+    counts = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), counts
+    len64 = text_len.to(torch.int64)
+    bad = ((text_off < 0) | (len64 < 0)
+           | (text_off + len64 > pool.numel())).any()
+    if bool(bad.item()):
+        raise ValueError("a text range lies outside the pool")
+    rc = lib.crawl_yt_scan_count(_vp(pool), _vp(text_off), _vp(text_len),
+                                 n, _vp(counts), _cur_stream())
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_scan_count failed: hip {rc}")
+    c64 = counts.to(torch.int64)
+    end = torch.cumsum(c64, 0)
+    out_base = (end - c64).contiguous()
+    total = int(end[-1].item())
+    hit_off = torch.empty(total, dtype=torch.int64, device=dev)
+    if total:
+        rc = lib.crawl_yt_scan_write(_vp(pool), _vp(text_off),
+                                     _vp(text_len), n, _vp(out_base),
+                                     _vp(hit_off), _cur_stream())
+        if rc != 0:
+            raise RuntimeError(f"crawl_yt_scan_write failed: hip {rc}")
+    return hit_off, counts
+
+
+class YtChannelReverseMap:
+    """Channel id -> channel index for a whole synthetic universe: the
+    device counterpart of ``SyntheticYouTubeIndex.channel_index_of`` with
+    every channel registered.
+
+    An open-addressing table of channel indices in HBM, built once per
+    ``(seed, universe)`` and sized for a load <= 0.5 (``slots_log2`` pins
+    the size instead: a full table raises :class:`YtClaimTableError`).
+    No strings are stored; a lookup regenerates the slot's id and
+    compares all 24 bytes. An id two indices share maps to the smaller."""
+
+    def __init__(self, index, device, slots_log2: Optional[int] = None):
+        self.device = torch.device(device)
+        assert self.device.type == "cuda"
+        self.seed = int(index.seed)
+        self.universe = int(index.universe)
+        if self.universe <= 0:
+            raise ValueError("the universe must hold at least one channel")
+        if slots_log2 is None:
+            slots_log2 = 1
+            while (1 << slots_log2) < 2 * self.universe:
+                slots_log2 += 1
+        self.slots_log2 = int(slots_log2)
+        self._lib = require_lib()
+        with torch.cuda.device(self.device):
+            self.table = torch.full((1 << self.slots_log2,), -1,
+                                    dtype=torch.int64, device=self.device)
+            err = torch.zeros(1, dtype=torch.int32, device=self.device)
+            rc = self._lib.crawl_yt_cid_table_build(
+                self.seed, self.universe, _vp(self.table), self.slots_log2,
+                _vp(err), _cur_stream())
+            if rc != 0:
+                raise RuntimeError(
+                    f"crawl_yt_cid_table_build failed: hip {rc}")
+            e = int(err.item())
+        if e:
+            raise YtClaimTableError(
+                f"channel reverse map error word {e:#x} "
+                f"(slots=2**{self.slots_log2}, universe={self.universe})")
+
+    def lookup(self, pool: torch.Tensor,
+               hit_off: torch.Tensor) -> torch.Tensor:
+        """Channel index of the 24 bytes at each ``pool`` offset (int64[m]
+        on the device), or -1 where they name no channel."""
+        assert pool.dtype == torch.uint8 and pool.device == self.device
+        assert hit_off.dtype == torch.int64 and hit_off.device == self.device
+        pool = pool.contiguous()
+        hit_off = hit_off.contiguous()
+        m = hit_off.numel()
+        out = torch.empty(m, dtype=torch.int64, device=self.device)
+        if m == 0:
+            return out
+        bad = ((hit_off < 0) | (hit_off + YT_CID_LEN > pool.numel())).any()
+        if bool(bad.item()):
+            raise ValueError("an id offset lies outside the pool")
+        rc = self._lib.crawl_yt_cid_lookup(
+            self.seed, _vp(pool), _vp(hit_off), m, _vp(self.table),
+            self.slots_log2, _vp(out), _cur_stream())
+        if rc != 0:
+            raise RuntimeError(f"crawl_yt_cid_lookup failed: hip {rc}")
+        return out
 
 
 def _bind_aux(lib):

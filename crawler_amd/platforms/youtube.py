@@ -18,7 +18,10 @@ class YouTubeCrawler(PlatformCrawler):
         from ..youtube.runner import run_youtube
 
         if getattr(ctx.args, "gpu", False):
-            if ctx.cfg.sampling_method in ("random", "channel"):
+            method = ctx.cfg.sampling_method
+            if method in ("random", "channel") or (
+                    method == "snowball"
+                    and getattr(ctx.args, "yt_gpu_snowball", False)):
                 from ..youtube.gpu_runner import run_youtube_gpu
 
                 stats = run_youtube_gpu(ctx.cfg, ctx.urls)
@@ -26,7 +29,8 @@ class YouTubeCrawler(PlatformCrawler):
                       file=sys.stderr)
                 return stats
             print("youtube: the GPU mode covers random and channel "
-                  "sampling; running snowball on the CPU",
+                  "sampling; running snowball on the CPU "
+                  "(--yt-gpu-snowball runs it on the GPU)",
                   file=sys.stderr)
         stats = run_youtube(ctx.cfg, ctx.urls)
         print(f"youtube crawl complete: {stats}", file=sys.stderr)

@@ -624,6 +624,35 @@ def yt_meta_from_ids_device(index: SyntheticYouTubeIndex,
     return m
 
 
+def yt_descriptions_from_ids_device(index: SyntheticYouTubeIndex,
+                                    ids_u8: torch.Tensor):
+    """The generated description bytes of the videos named by ``ids_u8``
+    (uint8[n,11] on the device): ``(pool, desc_off int64[n], desc_len
+    int32[n])``. The lighter sibling of :func:`build_batch_from_ids_device`
+    for callers that only read the texts: the same meta and fill kernels
+    and the same ``[vid | title | desc]`` layout, with no channel table."""
+    from ..ops import gpu as _g
+
+    lib = _g.require_lib()
+    dev = ids_u8.device
+    m = yt_meta_from_ids_device(index, ids_u8)
+    vid_pool, desc_len = m["vid_pool"], m["desc_len"]
+    n = vid_pool.shape[0]
+    p = _g._vp
+    ar = torch.arange(n, dtype=torch.int64, device=dev)
+    title_off = n * 11 + ar * 27
+    dl64 = desc_len.to(torch.int64)
+    desc_off = (torch.cumsum(dl64, 0) - dl64 + n * (11 + 27)).contiguous()
+    total = n * (11 + 27) + (int(dl64.sum().item()) if n else 0)
+    pool = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
+    rc = lib.crawl_yt_gen_fill_ids(
+        index.seed, index.universe, n, p(vid_pool), p(m["topic"]),
+        p(m["tnum"]), p(title_off), p(desc_off), p(pool), _g._cur_stream())
+    if rc != 0:
+        raise RuntimeError(f"crawl_yt_gen_fill_ids failed: hip {rc}")
+    return pool, desc_off, desc_len
+
+
 def build_batch_from_ids_device(index: SyntheticYouTubeIndex,
                                 ids_u8: torch.Tensor, device,
                                 crawl_label: str = "") -> YouTubeBatch:

@@ -1,11 +1,12 @@
-"""GPU execution mode for YouTube random and channel sampling.
+"""GPU execution mode for YouTube random, channel and snowball sampling.
 
 The device counterpart of :func:`crawler_amd.youtube.runner.run_youtube`
-for ``sampling_method`` ``random`` and ``channel``. For the same index,
-``min_channel_videos``, limit, ``max_searches``, ``daily_quota``, rng
-seed, crawl label and ``now`` it writes byte-identical per-channel
-``posts.jsonl`` files, returns the same stats dict and raises
-:class:`QuotaExceeded` where the CPU client lets one escape.
+for ``sampling_method`` ``random``, ``channel`` and ``snowball``. For the
+same index, ``min_channel_videos``, limit, ``max_searches``,
+``daily_quota``, ``max_depth``, rng seed, crawl label and ``now`` it
+writes byte-identical per-channel ``posts.jsonl`` files, returns the same
+stats dict and raises :class:`QuotaExceeded` where the CPU client lets
+one escape.
 
 Random sampling runs in ROUNDS of many prefixes (search, first-claim of
 the ids, first-claim of the channels: csrc/yt_sample.hip); only four
@@ -16,11 +17,27 @@ round draws all its prefixes before that search is known, so the GPU
 mode may consume MORE prefixes from the rng than the CPU loop does: the
 rng's end state differs, nothing else.
 
-Two deliberate differences from the CPU runner, both outside what it can
+Snowball sampling runs one BFS LAYER at a time (first-claim of the
+frontier's channel indices, uploads, then csrc/yt_snowball.hip: a scan of
+the layer's generated description bytes for ``UC...`` ids and a lookup of
+each hit in a device reverse map of the universe's channel ids). Only the
+per-channel upload counts come back to the host, where
+:class:`SnowballReplay` replays ``get_snowball_videos``' quota and the
+``limit`` cut. The CPU client's per-text dedup and its ``not in visited``
+filter on the next frontier are not mirrored: the frontier skips visited
+and repeated ids when it is consumed, so neither is observable.
+
+Deliberate differences from the CPU runner, all outside what it can
 express: an unknown ``UC...`` url raises ``ValueError`` (the CPU runner
-spends a unit and writes nothing), and in channel mode a video-channel
+spends a unit and writes nothing in channel mode, and crawls nothing from
+that seed in snowball mode); in channel and snowball mode a video-channel
 lookup that does not fit the quota raises ``QuotaExceeded`` (the CPU
-conversion pool swallows it and emits the post without channel data).
+conversion pool swallows it and emits the post without channel data);
+and snowball resolves a discovered id against the whole universe, where
+the CPU index knows only the ids it has generated so far (every id a
+generated description carries is one of those, so crawls agree; should
+two channel indices share an id, the device takes the smaller index and
+the CPU index the one registered last).
 """
 from __future__ import annotations
 
@@ -139,6 +156,47 @@ def replay_random_accounting(rows, limit: int, max_searches: int,
     return n, cut, dict(rp.stats), rp.quota_used
 
 
+class SnowballReplay:
+    """Integer replay of ``SyntheticYouTubeClient.get_snowball_videos``
+    over the upload counts of the channels it visits, in visiting order.
+
+    A channel with no uploads costs nothing; any other costs its
+    Videos.List units for the WHOLE channel before the ``limit`` cut is
+    looked at. ``videos`` is the number of videos to take so far (the
+    first ``videos`` uploads in channel order) and ``done`` is set once
+    the limit is reached: the client returns there."""
+
+    def __init__(self, limit: int, daily_quota: int):
+        self.limit = limit
+        self.daily_quota = daily_quota
+        self.quota_used = 0
+        self.videos = 0
+        self.done = limit <= 0
+        self.stats = {"searches": 0, "video_batches": 0,
+                      "channels_checked": 0, "gate_rejected": 0,
+                      "invalid_ids": 0}
+
+    _spend = RandomReplay._spend
+    _list_videos = RandomReplay._list_videos
+
+    def feed(self, counts: Sequence[int]) -> int:
+        """Consume per-channel upload counts until the limit cuts or they
+        run out; returns how many channels were consumed. Raises
+        QuotaExceeded where ``list_videos`` would."""
+        used = 0
+        for c in counts:
+            if self.done:
+                break
+            used += 1
+            if c <= 0:
+                continue
+            self._list_videos(c)
+            self.videos += min(c, self.limit - self.videos)
+            if self.videos >= self.limit:
+                self.done = True
+        return used
+
+
 # ---------- device side ----------
 
 def _floor_secs(t: _dt.datetime) -> Tuple[int, bool]:
@@ -147,6 +205,22 @@ def _floor_secs(t: _dt.datetime) -> Tuple[int, bool]:
     d = t - _EPOCH
     secs = d // _dt.timedelta(seconds=1)
     return secs, (d - _dt.timedelta(seconds=secs)) > _dt.timedelta(0)
+
+
+def _fanout_channels() -> int:
+    """Channels handed to the file sink in one call. The sink keeps up to
+    256 files open between calls and opens one more per channel during a
+    call, so a call gets at most half of the process's open-file limit
+    less those 256, and never more than 8192."""
+    try:
+        import resource
+
+        soft = resource.getrlimit(resource.RLIMIT_NOFILE)[0]
+    except (ImportError, OSError, ValueError):
+        return 128
+    if soft == resource.RLIM_INFINITY:
+        return 8192
+    return max(64, min(8192, soft // 2 - 256))
 
 
 def _resolve_channel_urls(index: SyntheticYouTubeIndex,
@@ -231,6 +305,77 @@ def _sample_channels(index, urls, limit, daily_quota, dev):
     return ids[take], rp, looked_up
 
 
+def _sample_snowball(index, urls, limit, max_depth, daily_quota, dev,
+                     claim_slots_log2, chunk_videos, timings):
+    import torch
+
+    from ..ops import gpu
+    from .batch import yt_descriptions_from_ids_device
+
+    ns = _resolve_channel_urls(index, urls)
+    if any(n < 0 for n in ns):
+        raise ValueError("a YouTube channel index cannot be negative")
+    rp = SnowballReplay(limit, daily_quota)
+    visited = gpu.YtFirstClaim(dev, slots_log2=claim_slots_log2)
+    rmap = None
+    accepted = []
+    frontier = torch.tensor(ns, dtype=torch.int64, device=dev)
+    k = torch.arange(gpu.YT_UPLOAD_SLOTS, device=dev)
+    base_idx = 0
+    depth = 0
+    # ``timings["snowball_steps"] = {}`` asks for the layer loop's own
+    # split; it costs a device synchronisation per step
+    steps = timings.get("snowball_steps")
+    t0 = _time.perf_counter()
+
+    def lap(name):
+        nonlocal t0
+        if steps is not None:
+            torch.cuda.synchronize(dev)
+            now_ = _time.perf_counter()
+            steps[name] = steps.get(name, 0.0) + now_ - t0
+            t0 = now_
+
+    while frontier.numel() and not rp.done and depth <= max_depth:
+        # `visited`: the frontier's first occurrences, in global order
+        first = visited.claim(frontier, None, base_idx).bool()
+        base_idx += int(frontier.numel())
+        chans = frontier[first]
+        lap("claim")
+        ids, counts = gpu.yt_uploads(index, chans, gpu.YT_UPLOAD_SLOTS)
+        before = rp.videos
+        rp.feed(counts.cpu().tolist())
+        layer = ids[k[None, :] < counts[:, None]][:rp.videos - before]
+        accepted.append(layer)
+        lap("uploads_replay")
+        depth += 1
+        if rp.done or depth > max_depth:
+            break
+        # discovery: scan the layer's description bytes, resolve the hits
+        if rmap is None:
+            rmap = gpu.YtChannelReverseMap(index, dev)
+            lap("reverse_map_build")
+        nxt = []
+        for c0 in range(0, int(layer.shape[0]), chunk_videos):
+            pool, d_off, d_len = yt_descriptions_from_ids_device(
+                index, layer[c0:c0 + chunk_videos])
+            lap("describe")
+            hit_off, _ = gpu.yt_scan_channel_ids(pool, d_off, d_len)
+            lap("scan")
+            n = rmap.lookup(pool, hit_off)
+            nxt.append(n[n >= 0])
+            lap("lookup")
+        frontier = (torch.cat(nxt) if nxt else
+                    torch.empty(0, dtype=torch.int64, device=dev))
+    timings["claim_grown"] = visited.grown
+    timings["snowball_layers"] = depth
+    if accepted:
+        ids = torch.cat(accepted)
+    else:
+        ids = torch.empty((0, 11), dtype=torch.uint8, device=dev)
+    return ids, rp
+
+
 def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
                     max_searches: Optional[int] = None,
                     daily_quota: Optional[int] = None,
@@ -238,11 +383,13 @@ def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
                     claim_slots_log2: int = 16, index=None,
                     chunk_videos: int = 1 << 18,
                     timings: Optional[dict] = None) -> dict:
-    """Random / channel YouTube sampling on the GPU; see the module doc.
+    """Random / channel / snowball YouTube sampling on the GPU; see the
+    module doc.
 
     ``round_searches`` prefixes are searched per round; ``chunk_videos``
     (<= 1M: the batch offsets are int32) bounds one generate+encode
-    batch. ``timings``, when given, receives the wall-clock split."""
+    batch and one snowball description scan. ``timings``, when given,
+    receives the wall-clock split."""
     import torch
 
     from ..config import calculate_date_filters
@@ -251,10 +398,10 @@ def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
     from .batch import build_batch_from_ids_device, yt_meta_from_ids_device
 
     method = cfg.sampling_method
-    if method not in ("random", "channel"):
+    if method not in ("random", "channel", "snowball"):
         raise ValueError(
-            f"the YouTube GPU mode covers random and channel sampling, "
-            f"not {method!r}")
+            f"the YouTube GPU mode covers random, channel and snowball "
+            f"sampling, not {method!r}")
     if not 1 <= chunk_videos <= 1_000_000:
         raise ValueError("chunk_videos must be in 1..1000000")
     seed = getattr(cfg, "synthetic_seed", 99)
@@ -280,6 +427,11 @@ def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
                 daily_quota, max(1, round_searches), dev,
                 claim_slots_log2, t)
             looked_up = None
+        elif method == "snowball":
+            ids, rp = _sample_snowball(
+                index, urls, limit, max(cfg.max_depth, 1), daily_quota,
+                dev, claim_slots_log2, chunk_videos, t)
+            looked_up = set()   # sampling never calls get_channel_info
         else:
             ids, rp, looked_up = _sample_channels(index, urls, limit,
                                                   daily_quota, dev)
@@ -311,6 +463,7 @@ def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
         t["sample"] += tick() - t0
 
         posts = 0
+        fanout_channels = _fanout_channels()
         ar24 = torch.arange(24, device=dev)
         for c0 in range(0, n_videos, chunk_videos):
             t0 = tick()
@@ -338,7 +491,12 @@ def run_youtube_gpu(cfg, urls: List[str], *, sm=None, rng=None, now=None,
             t0 = tick()
             items = [(cid_blob[24 * c:24 * c + 24], lo_h[c], hi_h[c])
                      for c in range(b.n_channels)]
-            sm.store_post_lines_batch(items, memoryview(buf))
+            # the sink closes surplus files only between calls, so one
+            # call must not open more files than the process may hold
+            mv = memoryview(buf)
+            for i0 in range(0, len(items), fanout_channels):
+                sm.store_post_lines_batch(items[i0:i0 + fanout_channels],
+                                          mv)
             posts += b.n
             t["fanout"] += tick() - t0
 

@@ -1,14 +1,17 @@
 #!/usr/bin/env python
 """End-to-end rate of the YouTube GPU crawl mode, disk included.
 
-Runs random sampling through youtube/gpu_runner.run_youtube_gpu at
---limit videos (quota lifted, max_searches high enough to reach it) and
-the CPU youtube/runner.run_youtube with the same flags at --cpu-limit
-(the CPU path does ~700 videos/s, so the full size would take tens of
-minutes). Prints videos/s for both and the GPU run's split: sampling
-rounds, generate+encode, D2H, file fan-out.
+Runs random (default) or snowball sampling through
+youtube/gpu_runner.run_youtube_gpu at --limit videos (quota lifted,
+max_searches high enough to reach it) and the CPU
+youtube/runner.run_youtube with the same flags at --cpu-limit (the CPU
+path does ~700 videos/s, so the full size would take tens of minutes).
+Prints videos/s for both and the GPU run's split: sampling (search rounds
+or snowball layers), generate+encode, D2H, file fan-out.
 
     python scripts/yt_gpu_crawl_bench.py --limit 1000000 --cpu-limit 10000
+    python scripts/yt_gpu_crawl_bench.py --sampling snowball \
+        --seeds 99,33,150 --max-depth 6 --limit 1000000 --cpu-limit 10000
 """
 import argparse
 import json
@@ -28,6 +31,15 @@ def main(argv=None) -> int:
                     help="0 skips the CPU run")
     ap.add_argument("--seed", type=int, default=99)
     ap.add_argument("--round-searches", type=int, default=65536)
+    ap.add_argument("--sampling", choices=["random", "snowball"],
+                    default="random")
+    ap.add_argument("--seeds", default="99,33,150",
+                    help="snowball: comma-separated seed channel indices")
+    ap.add_argument("--max-depth", type=int, default=6,
+                    help="snowball: BFS depth")
+    ap.add_argument("--snowball-steps", action="store_true",
+                    help="snowball: also time the layer loop's steps "
+                         "(a device synchronisation per step)")
     ap.add_argument("--storage-root", default="",
                     help="default: a temporary directory, removed after")
     args = ap.parse_args(argv)
@@ -40,30 +52,37 @@ def main(argv=None) -> int:
 
     root = args.storage_root or tempfile.mkdtemp(prefix="yt-gpu-bench-")
     big = 10 ** 15
+    urls = ([u for u in args.seeds.split(",") if u]
+            if args.sampling == "snowball" else [])
 
     def cfg(crawl_id, limit):
         # ~1.6 verified videos per search: 2x headroom on the searches
         return CrawlerConfig(
             storage_root=root, crawl_id=crawl_id, platform="youtube",
-            sampling_method="random", max_posts=limit, crawl_label="bench",
+            sampling_method=args.sampling, max_posts=limit,
+            max_depth=args.max_depth, crawl_label="bench",
             synthetic_seed=args.seed, yt_max_searches=2 * limit + 1000,
             yt_daily_quota=big)
 
     try:
         # warm the runtime (library load, allocator) outside the timing
-        run_youtube_gpu(cfg("warm", 256), [], round_searches=256)
+        run_youtube_gpu(cfg("warm", 256), urls, round_searches=256)
         timings = {}
+        if args.sampling == "snowball" and args.snowball_steps:
+            timings["snowball_steps"] = {}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        stats = run_youtube_gpu(cfg("gpu", args.limit), [],
+        stats = run_youtube_gpu(cfg("gpu", args.limit), urls,
                                 round_searches=args.round_searches,
                                 timings=timings)
         wall = time.perf_counter() - t0
         split = {k: round(timings[k], 4)
                  for k in ("sample", "gen_encode", "d2h", "fanout")}
         out = {
-            "mode": "gpu", "limit": args.limit,
+            "mode": "gpu", "sampling": args.sampling, "limit": args.limit,
             "videos": stats["videos"], "searches": stats["searches"],
+            "video_batches": stats["video_batches"],
+            "layers": timings.get("snowball_layers", 0),
             "wall_s": round(wall, 4),
             "videos_per_s": round(stats["videos"] / wall, 1),
             "split_s": split,
@@ -72,13 +91,17 @@ def main(argv=None) -> int:
                              / max(timings["d2h"], 1e-9) / 1e9, 3),
             "claim_grown": timings.get("claim_grown", 0),
         }
+        if "snowball_steps" in timings:
+            out["sample_steps_s"] = {k: round(v, 4) for k, v in
+                                     timings["snowball_steps"].items()}
         print(json.dumps(out), flush=True)
         if args.cpu_limit > 0:
             t0 = time.perf_counter()
-            cstats = run_youtube(cfg("cpu", args.cpu_limit), [])
+            cstats = run_youtube(cfg("cpu", args.cpu_limit), urls)
             cwall = time.perf_counter() - t0
             print(json.dumps({
-                "mode": "cpu", "limit": args.cpu_limit,
+                "mode": "cpu", "sampling": args.sampling,
+                "limit": args.cpu_limit,
                 "videos": cstats["videos"],
                 "searches": cstats["searches"],
                 "wall_s": round(cwall, 4),
