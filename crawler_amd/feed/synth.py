@@ -358,7 +358,6 @@ class SyntheticFeed:
 
         from ..ops import gpu as gpu_mod
 
-        lib = gpu_mod.require_lib()
         cfg = self.cfg
         P = posts_per_channel or cfg.posts_per_channel
         K = len(channel_ids)
@@ -369,9 +368,8 @@ class SyntheticFeed:
             "device generator"
         )
         tables = self._device_tables(device)
-        tbl_ptrs = (ctypes.c_void_p * len(self._TBL_ORDER))()
-        for k, name in enumerate(self._TBL_ORDER):
-            tbl_ptrs[k] = ctypes.c_void_p(tables[name].data_ptr())
+        tbl_ptrs = gpu_mod._ptr_array(
+            [tables[name] for name in self._TBL_ORDER])
         scalars = (ctypes.c_long * 10)(
             len(self.templates), len(self._comment_bytes), cfg.seed,
             cfg.universe, cfg.base_date, cfg.date_step, int(permille),
@@ -379,28 +377,22 @@ class SyntheticFeed:
         )
         cids_t = T.tensor(np.asarray(channel_ids, dtype=np.int64),
                           device=device)
-        stream = ctypes.c_void_p(T.cuda.current_stream().cuda_stream)
 
         z64 = lambda n: T.zeros(n, dtype=T.int64, device=device)
         z32 = lambda n: T.zeros(n, dtype=T.int32, device=device)
         chat_id, msg_id, block_len = z64(N), z64(N), z64(N)
         m = {f: z32(N) for f in B._META_FIELDS_I32}
         tidx = z32(N)
-        out_ptrs = (ctypes.c_void_p * 18)(
-            *[ctypes.c_void_p(x.data_ptr()) for x in [
-                chat_id, msg_id, m["date"], m["content_type"], m["views"],
-                m["forwards"], m["media_album_id"], m["channel_idx"],
-                m["flags"], m["text_len"], m["aux_len"], m["ent_cnt"],
-                m["react_cnt"], m["com_cnt"], m["poster_len"],
-                m["reply_count"], block_len, tidx,
-            ]]
-        )
+        out_ptrs = gpu_mod._ptr_array([
+            chat_id, msg_id, m["date"], m["content_type"], m["views"],
+            m["forwards"], m["media_album_id"], m["channel_idx"],
+            m["flags"], m["text_len"], m["aux_len"], m["ent_cnt"],
+            m["react_cnt"], m["com_cnt"], m["poster_len"],
+            m["reply_count"], block_len, tidx,
+        ])
         grid = min((N + 255) // 256, 8192)
-        rc = lib.crawl_feed_meta(tbl_ptrs, scalars,
-                                 ctypes.c_void_p(cids_t.data_ptr()),
-                                 out_ptrs, grid, stream)
-        if rc != 0:
-            raise RuntimeError(f"crawl_feed_meta failed: hip {rc}")
+        gpu_mod._call("crawl_feed_meta", tbl_ptrs, scalars, cids_t, out_ptrs,
+                      grid)
 
         def excl_cumsum(x64):
             out = T.zeros(x64.numel() + 1, dtype=T.int64, device=device)
@@ -445,22 +437,13 @@ class SyntheticFeed:
             (0, 5), dtype=T.int32, device=device)
         ent_store = entities if E else z32(5).view(1, 5)
         react_emoji, react_count = z32(max(R, 1)), z32(max(R, 1))
-        fill_ptrs = (ctypes.c_void_p * 9)(
-            *[ctypes.c_void_p(x.data_ptr()) for x in [
-                pool, text_off, m["aux_off"], m["poster_off"], m["ent_off"],
-                m["react_off"], ent_store, react_emoji, react_count,
-            ]]
-        )
-        rc = lib.crawl_feed_fill(
-            tbl_ptrs, scalars, ctypes.c_void_p(cids_t.data_ptr()),
-            ctypes.c_void_p(tidx.data_ptr()),
-            ctypes.c_void_p(block_off.data_ptr()),
-            ctypes.c_void_p(ent_off_l.data_ptr()),
-            ctypes.c_void_p(react_off_l.data_ptr()),
-            fill_ptrs, min((N + 3) // 4, 8192), stream,
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_feed_fill failed: hip {rc}")
+        fill_ptrs = gpu_mod._ptr_array([
+            pool, text_off, m["aux_off"], m["poster_off"], m["ent_off"],
+            m["react_off"], ent_store, react_emoji, react_count,
+        ])
+        gpu_mod._call("crawl_feed_fill", tbl_ptrs, scalars, cids_t, tidx,
+                      block_off, ent_off_l, react_off_l, fill_ptrs,
+                      min((N + 3) // 4, 8192))
 
         com = {f: z32(max(C, 1)) for f in [
             "text_off", "text_len", "handle_off", "handle_len", "views",
@@ -469,21 +452,14 @@ class SyntheticFeed:
             cmsg_of = T.repeat_interleave(
                 T.arange(N, dtype=T.int64, device=device),
                 m["com_cnt"].to(T.int64))
-            com_ptrs = (ctypes.c_void_p * 9)(
-                *[ctypes.c_void_p(x.data_ptr()) for x in [
-                    pool, com["text_off"], com["text_len"],
-                    com["handle_off"], com["handle_len"], com["views"],
-                    com["replies"], com["react_off"], com["react_cnt"],
-                ]]
-            )
-            rc = lib.crawl_feed_comments(
-                tbl_ptrs, scalars, ctypes.c_void_p(cids_t.data_ptr()),
-                ctypes.c_void_p(com_off_l.data_ptr()), cblock,
-                ctypes.c_void_p(cmsg_of.data_ptr()), msg_total, C,
-                com_ptrs, min((C + 255) // 256, 8192), stream,
-            )
-            if rc != 0:
-                raise RuntimeError(f"crawl_feed_comments failed: hip {rc}")
+            com_ptrs = gpu_mod._ptr_array([
+                pool, com["text_off"], com["text_len"],
+                com["handle_off"], com["handle_len"], com["views"],
+                com["replies"], com["react_off"], com["react_cnt"],
+            ])
+            gpu_mod._call("crawl_feed_comments", tbl_ptrs, scalars, cids_t,
+                          com_off_l, cblock, cmsg_of, msg_total, C, com_ptrs,
+                          min((C + 255) // 256, 8192))
 
         m["com_off"] = com_off_l[:-1].to(T.int32)
         t = lambda arr, dt_: T.tensor(arr, dtype=dt_, device=device)

@@ -21,9 +21,9 @@ def needs_build() -> bool:
     if not os.path.exists(OUT):
         return True
     out_m = os.path.getmtime(OUT)
-    deps = [os.path.join(CSRC, s) for s in SOURCES]
-    deps += [os.path.join(CSRC, h) for h in ("common.h", "yt_hash.h")]
-    return any(os.path.getmtime(d) > out_m for d in deps)
+    deps = SOURCES + [f for f in os.listdir(CSRC) if f.endswith(".h")]
+    return any(os.path.getmtime(os.path.join(CSRC, d)) > out_m
+               for d in deps)
 
 
 def build(force: bool = False) -> str:

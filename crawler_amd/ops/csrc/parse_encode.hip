@@ -804,8 +804,8 @@ compact_kernel(const unsigned char* scratch, long stride,
 // ---- C ABI (ctypes-friendly; torch-header-free) ----
 //
 // Pointer/scalar array layouts MUST stay in sync with ops/gpu.py
-// (_BATCH_PTR_ORDER / _SCALAR_ORDER). The Python side passes
-// tensor.data_ptr() values in that order.
+// (_BATCH_PTR_ORDER, and the ``scalars`` array parse_encode builds). The
+// Python side passes tensor.data_ptr() values in that order.
 
 namespace crawl {
 

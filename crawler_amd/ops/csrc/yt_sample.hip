@@ -8,10 +8,9 @@
 //                          channel cache)
 //   crawl_yt_claim_insert  pass 1 alone (re-insert on table growth)
 //   crawl_yt_uploads       channel_uploads, 29 slots per channel
-//   crawl_yt_gen_meta_ids / crawl_yt_gen_fill_ids
-//                          the yt_feedgen.hip meta/fill kernels driven by
-//                          an id array instead of the i0 prefix walk
-//   crawl_yt_chan_lens     channel-table string lengths
+//
+// The ids found here become batches through the generator kernels of
+// yt_feedgen.hip; the index's hash helpers are in yt_hash.h.
 //
 // One thread per output element, 256-thread blocks. Every entry point
 // returns hipGetLastError() and launches nothing for a zero count.
@@ -24,10 +23,6 @@ namespace crawl {
 #define YT_UPLOAD_SLOTS 29
 #define YT_CLAIM_EMPTY 0xFFFFFFFFFFFFFFFFULL
 
-DEV unsigned long long yt_base(long long seed) {
-  return (unsigned long long)seed ^ 0xC0FFEEULL;
-}
-
 // index of c in YT_ALPH, or -1
 DEV int yt_alph_index(unsigned char c) {
   if (c >= 'a' && c <= 'z') return c - 'a';
@@ -36,30 +31,6 @@ DEV int yt_alph_index(unsigned char c) {
   if (c == '-') return 62;
   if (c == '_') return 63;
   return -1;
-}
-
-// video_id(prefix, k): prefix + '-' + 5 hash chars
-DEV void yt_video_id(unsigned long long base, const unsigned char* pc,
-                     unsigned long long k, unsigned char* vid) {
-  unsigned long long a = yt_chain(base, "vid");
-  for (int j = 0; j < 5; ++j) a = yt_smx(a ^ (unsigned long long)pc[j]);
-  unsigned long long h1 = yt_smx(a ^ k);
-  for (int j = 0; j < 5; ++j) vid[j] = pc[j];
-  vid[5] = '-';
-  for (int j = 0; j < 5; ++j)
-    vid[6 + j] = (unsigned char)YT_ALPH[(h1 >> (6 * j)) % 64ULL];
-}
-
-DEV unsigned long long yt_vidmeta_hash(unsigned long long base,
-                                       const unsigned char* vid) {
-  unsigned long long a = yt_chain(base, "vidmeta");
-  for (int j = 0; j < 11; ++j) a = yt_smx(a ^ (unsigned long long)vid[j]);
-  return a;
-}
-
-DEV int yt_video_count(unsigned long long base, unsigned long long n) {
-  unsigned long long hc = yt_smx(yt_chain(base, "chanmeta") ^ n);
-  return (int)((hc >> 20) % 30ULL);
 }
 
 // ---------- search ----------
@@ -228,90 +199,6 @@ __global__ void __launch_bounds__(256) yt_uploads_kernel(
   for (int i = 0; i < 11; ++i) ids[t * 11 + i] = vid[i];
 }
 
-// ---------- id-driven meta / fill (yt_feedgen.hip semantics) ----------
-
-__global__ void __launch_bounds__(256) yt_gen_meta_ids_kernel(
-    long long seed, long long universe, long long base_date, long long n,
-    const unsigned char* vid_pool /*[n,11]*/, long long* published,
-    long long* views, int* likes, int* comments, int* duration_s,
-    int* lang, long long* n_chan, int* topic, int* tnum, int* desc_len) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned char vid[11];
-  for (int j = 0; j < 11; ++j) vid[j] = vid_pool[i * 11 + j];
-  unsigned long long h = yt_vidmeta_hash(yt_base(seed), vid);
-  n_chan[i] = (long long)(h % (unsigned long long)universe);
-  int secs = (int)((h >> 8) % 7200ULL);
-  duration_s[i] = secs ? secs : -1;
-  published[i] = base_date + (long long)(h % 10000000ULL);
-  views[i] = (long long)(h % 1000000ULL);
-  likes[i] = (int)((h >> 12) % 50000ULL);
-  comments[i] = (int)((h >> 22) % 5000ULL);
-  lang[i] = (h % 4ULL) == 0 ? 1 : 0;  // LANGS: 0=en, 1=ru
-  int tp = (int)(h % 1000ULL);
-  int tn = (int)(h % 97ULL);
-  topic[i] = tp;
-  tnum[i] = tn;
-  int dtp = tp >= 100 ? 3 : (tp >= 10 ? 2 : 1);
-  int dtn = tn >= 10 ? 2 : 1;
-  desc_len[i] = 18 + dtp + 29 + dtn + 45 + 24;
-}
-
-__global__ void __launch_bounds__(256) yt_gen_fill_ids_kernel(
-    long long seed, long long universe, long long n,
-    const unsigned char* vid_pool, const int* topic, const int* tnum,
-    const long long* title_off, const long long* desc_off,
-    unsigned char* pool) {
-  long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  unsigned char vid[11];
-  for (int j = 0; j < 11; ++j) vid[j] = vid_pool[i * 11 + j];
-  for (int j = 0; j < 11; ++j) pool[i * 11 + j] = vid[j];
-  const char* tp = "Synthetic video ";
-  unsigned char* t = pool + title_off[i];
-  for (int j = 0; j < 16; ++j) t[j] = (unsigned char)tp[j];
-  for (int j = 0; j < 11; ++j) t[16 + j] = vid[j];
-  unsigned char* d = pool + desc_off[i];
-  const char* s1 = "Video about topic ";
-  const char* s2 = ". More: https://example.com/t";
-  const char* s3 = " and channel https://www.youtube.com/channel/";
-  int c = 0;
-  for (const char* p = s1; *p; ++p) d[c++] = (unsigned char)*p;
-  c += yt_itoa(d + c, topic[i]);
-  for (const char* p = s2; *p; ++p) d[c++] = (unsigned char)*p;
-  c += yt_itoa(d + c, tnum[i]);
-  for (const char* p = s3; *p; ++p) d[c++] = (unsigned char)*p;
-  unsigned long long base = yt_base(seed);
-  unsigned long long h = yt_vidmeta_hash(base, vid);
-  yt_cid(base, yt_chain(base, "chan"),
-         (long long)((h >> 13) % (unsigned long long)universe), d + c);
-}
-
-// channel-table string lengths: title "Synthetic YT Channel <n>", desc
-// "Channel <n> description \xe2\x80\x94 see also UC friends", country
-// "US" iff hc % 3 == 0
-__global__ void __launch_bounds__(256) yt_chan_lens_kernel(
-    long long seed, const long long* chan_ns, long long K,
-    long long* title_len, long long* desc_len, long long* country_len) {
-  long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= K) return;
-  unsigned long long n = (unsigned long long)chan_ns[c];
-  unsigned long long hc = yt_smx(yt_chain(yt_base(seed), "chanmeta") ^ n);
-  int digs = u64_dec_len(n);
-  title_len[c] = 21 + digs;
-  desc_len[c] = 8 + digs + 36;
-  country_len[c] = (hc % 3ULL == 0ULL) ? 2 : 0;
-}
-
-// 64-bit grid size for one thread per element; 0 = do not launch
-static inline bool yt_grid(long long n, unsigned int* grid) {
-  if (n <= 0) return false;
-  long long g = (n + 255) / 256;
-  if (g > 0x7FFFFFFFLL) return false;
-  *grid = (unsigned int)g;
-  return true;
-}
-
 }  // namespace crawl
 
 extern "C" {
@@ -323,7 +210,7 @@ int crawl_yt_search(long long seed, long long universe,
   unsigned int grid;
   if (S <= 0) return (int)hipGetLastError();
   if (S > (1LL << 40) || universe <= 0 ||
-      !crawl::yt_grid(S * YT_SEARCH_SLOTS, &grid))
+      !crawl::yt_grid(S * YT_SEARCH_SLOTS, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_search_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, seed, universe,
@@ -341,7 +228,7 @@ int crawl_yt_claim_insert(const void* keys_in, const void* mask,
                           void* stream) {
   unsigned int grid;
   if (n <= 0) return (int)hipGetLastError();
-  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_grid(n, &grid))
+  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_grid(n, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_claim_insert_kernel, dim3(grid), dim3(256),
                      0, (hipStream_t)stream,
@@ -359,7 +246,7 @@ int crawl_yt_first_claim(const void* keys_in, const void* mask,
                          void* err, void* stream) {
   unsigned int grid;
   if (n <= 0) return (int)hipGetLastError();
-  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_grid(n, &grid))
+  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_grid(n, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_claim_insert_kernel, dim3(grid), dim3(256),
                      0, (hipStream_t)stream,
@@ -384,61 +271,13 @@ int crawl_yt_uploads(long long seed, const void* chans, long long K,
                      int limit, void* ids, void* counts, void* stream) {
   unsigned int grid;
   if (K <= 0) return (int)hipGetLastError();
-  if (K > (1LL << 40) || !crawl::yt_grid(K * YT_UPLOAD_SLOTS, &grid))
+  if (K > (1LL << 40) ||
+      !crawl::yt_grid(K * YT_UPLOAD_SLOTS, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_uploads_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, seed, (const long long*)chans,
                      K * YT_UPLOAD_SLOTS, limit, (unsigned char*)ids,
                      (int*)counts);
-  return (int)hipGetLastError();
-}
-
-int crawl_yt_gen_meta_ids(long long seed, long long universe,
-                          long long base_date, long long n,
-                          const void* vid_pool, void* published,
-                          void* views, void* likes, void* comments,
-                          void* duration_s, void* lang, void* n_chan,
-                          void* topic, void* tnum, void* desc_len,
-                          void* stream) {
-  unsigned int grid;
-  if (n <= 0) return (int)hipGetLastError();
-  if (universe <= 0 || !crawl::yt_grid(n, &grid))
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(crawl::yt_gen_meta_ids_kernel, dim3(grid), dim3(256),
-                     0, (hipStream_t)stream, seed, universe, base_date, n,
-                     (const unsigned char*)vid_pool, (long long*)published,
-                     (long long*)views, (int*)likes, (int*)comments,
-                     (int*)duration_s, (int*)lang, (long long*)n_chan,
-                     (int*)topic, (int*)tnum, (int*)desc_len);
-  return (int)hipGetLastError();
-}
-
-int crawl_yt_gen_fill_ids(long long seed, long long universe, long long n,
-                          const void* vid_pool, const void* topic,
-                          const void* tnum, const void* title_off,
-                          const void* desc_off, void* pool, void* stream) {
-  unsigned int grid;
-  if (n <= 0) return (int)hipGetLastError();
-  if (universe <= 0 || !crawl::yt_grid(n, &grid))
-    return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(crawl::yt_gen_fill_ids_kernel, dim3(grid), dim3(256),
-                     0, (hipStream_t)stream, seed, universe, n,
-                     (const unsigned char*)vid_pool, (const int*)topic,
-                     (const int*)tnum, (const long long*)title_off,
-                     (const long long*)desc_off, (unsigned char*)pool);
-  return (int)hipGetLastError();
-}
-
-int crawl_yt_chan_lens(long long seed, const void* chan_ns, long long K,
-                       void* title_len, void* desc_len, void* country_len,
-                       void* stream) {
-  unsigned int grid;
-  if (K <= 0) return (int)hipGetLastError();
-  if (!crawl::yt_grid(K, &grid)) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(crawl::yt_chan_lens_kernel, dim3(grid), dim3(256), 0,
-                     (hipStream_t)stream, seed, (const long long*)chan_ns,
-                     K, (long long*)title_len, (long long*)desc_len,
-                     (long long*)country_len);
   return (int)hipGetLastError();
 }
 

@@ -23,10 +23,6 @@ namespace crawl {
 #define YT_CID_EMPTY 0xFFFFFFFFFFFFFFFFULL
 #define YT_SCAN_WAVES 4
 
-DEV unsigned long long yt_sb_base(long long seed) {
-  return (unsigned long long)seed ^ 0xC0FFEEULL;
-}
-
 // [0-9A-Za-z_-]; a byte >= 0x80 is never a class byte
 DEV bool yt_cid_class(unsigned char c) {
   return (c >= '0' && c <= '9') || (c >= 'A' && c <= 'Z') ||
@@ -135,7 +131,7 @@ __global__ void __launch_bounds__(256) yt_cid_table_build_kernel(
     unsigned long long cap, unsigned int* err) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= universe) return;
-  unsigned long long base = yt_sb_base(seed);
+  unsigned long long base = yt_base(seed);
   unsigned long long a_chan = yt_chain(base, "chan");
   unsigned char id[YT_CID_LEN];
   yt_cid(base, a_chan, i, id);
@@ -165,7 +161,7 @@ __global__ void __launch_bounds__(256) yt_cid_lookup_kernel(
     long long* out_n) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
-  unsigned long long base = yt_sb_base(seed);
+  unsigned long long base = yt_base(seed);
   unsigned long long a_chan = yt_chain(base, "chan");
   unsigned char id[YT_CID_LEN];
   const unsigned char* src = pool + hit_off[i];
@@ -187,16 +183,6 @@ __global__ void __launch_bounds__(256) yt_cid_lookup_kernel(
   out_n[i] = found;
 }
 
-// grid for `per` elements per block; false = do not launch
-static inline bool yt_sb_grid(long long n, long long per,
-                              unsigned int* grid) {
-  if (n <= 0) return false;
-  long long g = (n + per - 1) / per;
-  if (g > 0x7FFFFFFFLL) return false;
-  *grid = (unsigned int)g;
-  return true;
-}
-
 }  // namespace crawl
 
 extern "C" {
@@ -207,7 +193,7 @@ int crawl_yt_scan_count(const void* pool, const void* text_off,
                         void* stream) {
   unsigned int grid;
   if (n <= 0) return (int)hipGetLastError();
-  if (!crawl::yt_sb_grid(n, YT_SCAN_WAVES, &grid))
+  if (!crawl::yt_grid(n, YT_SCAN_WAVES, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_scan_kernel<false>, dim3(grid),
                      dim3(64 * YT_SCAN_WAVES), 0, (hipStream_t)stream,
@@ -225,7 +211,7 @@ int crawl_yt_scan_write(const void* pool, const void* text_off,
                         void* stream) {
   unsigned int grid;
   if (n <= 0) return (int)hipGetLastError();
-  if (!crawl::yt_sb_grid(n, YT_SCAN_WAVES, &grid))
+  if (!crawl::yt_grid(n, YT_SCAN_WAVES, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_scan_kernel<true>, dim3(grid),
                      dim3(64 * YT_SCAN_WAVES), 0, (hipStream_t)stream,
@@ -243,7 +229,7 @@ int crawl_yt_cid_table_build(long long seed, long long universe,
   unsigned int grid;
   if (universe <= 0) return (int)hipGetLastError();
   if (cap_log2 < 1 || cap_log2 > 40 ||
-      !crawl::yt_sb_grid(universe, 256, &grid))
+      !crawl::yt_grid(universe, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_cid_table_build_kernel, dim3(grid),
                      dim3(256), 0, (hipStream_t)stream, seed, universe,
@@ -259,7 +245,7 @@ int crawl_yt_cid_lookup(long long seed, const void* pool,
                         void* stream) {
   unsigned int grid;
   if (m <= 0) return (int)hipGetLastError();
-  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_sb_grid(m, 256, &grid))
+  if (cap_log2 < 1 || cap_log2 > 40 || !crawl::yt_grid(m, 256, &grid))
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(crawl::yt_cid_lookup_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, seed,

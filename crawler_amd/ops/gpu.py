@@ -40,6 +40,68 @@ _BATCH_PTR_ORDER = [
 
 _lib = None
 
+# Every extern "C" entry point of csrc/*.hip -> its argument types, in the
+# C definition's order; all return int (tests/test_gpu_bindings.py pins
+# the names and counts to the sources). The last argument of every
+# launching entry point is the stream.
+_vp_t, _ll, _cl, _ci = (ctypes.c_void_p, ctypes.c_longlong, ctypes.c_long,
+                        ctypes.c_int)
+_pp = ctypes.POINTER(ctypes.c_void_p)   # void**: a pointer array
+_lp = ctypes.POINTER(ctypes.c_long)     # const long*: a scalar array
+_SIGNATURES = {
+    # parse_encode.hip
+    "crawl_batch_ptr_count": [],
+    "crawl_stage_budget": [],
+    "crawl_measure_extract": [_pp, _lp, _pp, _vp_t, _ci, _vp_t],
+    "crawl_write": [_pp, _lp, _pp, _vp_t, _vp_t, _vp_t, _ci, _vp_t],
+    "crawl_write_lds": [_pp, _lp, _pp, _vp_t, _vp_t, _vp_t, _ci, _vp_t],
+    "crawl_write_staged": [_pp, _lp, _pp, _vp_t, _vp_t, _vp_t, _ci, _ci,
+                           _ci, _ci, _ci, _vp_t],
+    "crawl_write_scratch": [_pp, _lp, _pp, _vp_t, _cl, _vp_t, _vp_t, _ci,
+                            _vp_t],
+    "crawl_compact": [_vp_t, _cl, _vp_t, _vp_t, _vp_t, _ci, _ci, _vp_t],
+    # dedup.hip
+    "crawl_claim_links": [_vp_t, _vp_t, _ci, _ci, _vp_t, _ll, _vp_t, _vp_t,
+                          _ci, _vp_t],
+    "crawl_bloom_update": [_vp_t, _vp_t, _ci, _ci, _vp_t, _ll, _ci, _vp_t],
+    "crawl_claim_compact": [_vp_t, _vp_t, _vp_t, _vp_t, _ci, _ci, _vp_t,
+                            _vp_t, _vp_t, ctypes.c_uint, _ci, _vp_t],
+    "crawl_insert_hashes": [_vp_t, _cl, _vp_t, _ll, _ci, _vp_t],
+    # feedgen.hip
+    "crawl_feed_meta": [_pp, _lp, _vp_t, _pp, _ci, _vp_t],
+    "crawl_feed_fill": [_pp, _lp] + [_vp_t] * 5 + [_pp, _ci, _vp_t],
+    "crawl_feed_comments": [_pp, _lp, _vp_t, _vp_t, _cl, _vp_t, _cl, _cl,
+                            _pp, _ci, _vp_t],
+    # aggregate.hip, sample.hip, htmlclass.hip
+    "crawl_channel_stats": [_vp_t] * 4 + [_ci, _ci] + [_vp_t] * 5 + [_vp_t],
+    "crawl_reservoir_sample": [_cl, _ci, _ci, _ci, _vp_t, _ci, _vp_t],
+    "crawl_html_classify": [_vp_t, _vp_t, _vp_t, _ci, _vp_t, _vp_t, _ci,
+                            _vp_t],
+    # yt_encode.hip
+    "crawl_yt_ptr_count": [],
+    "crawl_yt_measure": [_pp, _lp, _vp_t, _ci, _vp_t],
+    "crawl_yt_write": [_pp, _lp, _vp_t, _vp_t, _ci, _vp_t],
+    # yt_feedgen.hip
+    "crawl_yt_gen_ids": [_ll, _ll, _ll, _vp_t, _vp_t],
+    "crawl_yt_gen_meta": [_ll] * 4 + [_vp_t] * 11 + [_vp_t],
+    "crawl_yt_gen_fill": [_ll] * 3 + [_vp_t] * 6 + [_vp_t],
+    "crawl_yt_chan_lens": [_ll, _vp_t, _ll, _vp_t, _vp_t, _vp_t, _vp_t],
+    "crawl_yt_gen_channels": [_ll, _ll, _vp_t, _ll] + [_vp_t] * 9 + [_vp_t],
+    # yt_sample.hip
+    "crawl_yt_search": [_ll, _ll, _vp_t, _ll] + [_vp_t] * 5 + [_vp_t],
+    "crawl_yt_claim_insert": [_vp_t, _vp_t, _vp_t, _ll, _ll, _vp_t, _vp_t,
+                              _ci, _vp_t, _vp_t],
+    "crawl_yt_first_claim": [_vp_t, _vp_t, _ll, _ll, _vp_t, _vp_t, _ci,
+                             _vp_t, _vp_t, _vp_t],
+    "crawl_yt_uploads": [_ll, _vp_t, _ll, _ci, _vp_t, _vp_t, _vp_t],
+    # yt_snowball.hip
+    "crawl_yt_scan_count": [_vp_t, _vp_t, _vp_t, _ll, _vp_t, _vp_t],
+    "crawl_yt_scan_write": [_vp_t, _vp_t, _vp_t, _ll, _vp_t, _vp_t, _vp_t],
+    "crawl_yt_cid_table_build": [_ll, _ll, _vp_t, _ci, _vp_t, _vp_t],
+    "crawl_yt_cid_lookup": [_ll, _vp_t, _vp_t, _ll, _vp_t, _ci, _vp_t,
+                            _vp_t],
+}
+
 
 def lib_available() -> bool:
     return os.path.exists(_LIB_PATH)
@@ -50,81 +112,45 @@ def load_lib():
     if _lib is not None:
         return _lib
     lib = ctypes.CDLL(_LIB_PATH)
-    lib.crawl_batch_ptr_count.restype = ctypes.c_int
-    lib.crawl_measure_extract.restype = ctypes.c_int
-    lib.crawl_measure_extract.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.crawl_write.restype = ctypes.c_int
-    lib.crawl_write.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_write_staged.restype = ctypes.c_int
-    lib.crawl_write_staged.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_stage_budget.restype = ctypes.c_int
-    _bind_dedup(lib)
-    _bind_feedgen(lib)
-    _bind_v2(lib)
-    _bind_yt(lib)
-    _bind_yt_sample(lib)
-    _bind_aux(lib)
+    for name, argtypes in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_int
+        fn.argtypes = argtypes
     _lib = lib
     return lib
 
 
-def _bind_v2(lib):
-    lib.crawl_write_lds.restype = ctypes.c_int
-    lib.crawl_write_lds.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_write_scratch.restype = ctypes.c_int
-    lib.crawl_write_scratch.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_long,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_compact.restype = ctypes.c_int
-    lib.crawl_compact.argtypes = [
-        ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-    ]
+def require_lib():
+    """On a GPU host, a missing/failed extension is an ERROR, not a fallback."""
+    if _lib is None and not lib_available():
+        raise RuntimeError(
+            "libcrawlhip.so not built — run __graft_entry__.build() "
+            "(hipcc --offload-arch=gfx950) before GPU execution; the Python "
+            "golden path is not a substitute on GPU hosts"
+        )
+    return load_lib()
 
 
-def _bind_yt(lib):
-    for fn in ("crawl_yt_gen_meta", "crawl_yt_gen_fill",
-               "crawl_yt_gen_channels"):
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.crawl_yt_gen_meta.argtypes = (
-        [ctypes.c_longlong] * 5 + [ctypes.c_void_p] * 11
-        + [ctypes.c_void_p])
-    lib.crawl_yt_gen_fill.argtypes = (
-        [ctypes.c_longlong] * 5 + [ctypes.c_void_p] * 6
-        + [ctypes.c_void_p])
-    lib.crawl_yt_gen_channels.argtypes = (
-        [ctypes.c_longlong] * 3 + [ctypes.c_void_p, ctypes.c_longlong]
-        + [ctypes.c_void_p] * 9 + [ctypes.c_void_p])
-    lib.crawl_yt_ptr_count.restype = ctypes.c_int
-    lib.crawl_yt_measure.restype = ctypes.c_int
-    lib.crawl_yt_measure.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_yt_write.restype = ctypes.c_int
-    lib.crawl_yt_write.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
+def _cur_stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _vp(t: Optional[torch.Tensor]):
+    return ctypes.c_void_p(None if t is None else t.data_ptr())
+
+
+def _call(name: str, *args, stream: Optional[torch.cuda.Stream] = None):
+    """Run the launching entry point ``name``: tensor arguments (or None)
+    pass as their device pointers, and the stream argument that ends every
+    such signature is ``stream``, by default the current one. A non-zero
+    return raises."""
+    args = [_vp(a) if a is None or isinstance(a, torch.Tensor) else a
+            for a in args]
+    args.append(_cur_stream() if stream is None
+                else ctypes.c_void_p(stream.cuda_stream))
+    rc = getattr(require_lib(), name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed: hip {rc}")
 
 
 # Must match crawl::yt_make_view() in csrc/yt_encode.hip.
@@ -188,61 +214,20 @@ def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
     )
     if grid <= 0:
         grid = min((n + 3) // 4, 8192)
-    stream_ptr = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
     line_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    rc = lib.crawl_yt_measure(ptrs, scalars,
-                              ctypes.c_void_p(line_len.data_ptr()),
-                              grid, stream_ptr)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_measure failed: hip {rc}")
+    _call("crawl_yt_measure", ptrs, scalars, line_len, grid)
     line_off = torch.zeros(n, dtype=torch.int64, device=dev)
     torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
     total = int(line_off[-1].item() + line_len[-1].item())
     out, raw = _alloc_out(total, dev, _poison, _guard)
-    rc = lib.crawl_yt_write(ptrs, scalars,
-                            ctypes.c_void_p(line_off.data_ptr()),
-                            ctypes.c_void_p(out.data_ptr()),
-                            grid, stream_ptr)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_write failed: hip {rc}")
+    _call("crawl_yt_write", ptrs, scalars, line_off, out, grid)
     return YtEncodeResult(out, line_off, line_len, raw)
-
 
 
 # ---------- YouTube sampling (csrc/yt_sample.hip) ----------
 
 YT_SEARCH_SLOTS = 17   # n_valid <= 5, n_noise <= 12
 YT_UPLOAD_SLOTS = 29   # video_count <= 29
-
-
-def _bind_yt_sample(lib):
-    vp, ll, ci = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int
-    sigs = {
-        "crawl_yt_search": [ll, ll, vp, ll] + [vp] * 5 + [vp],
-        "crawl_yt_claim_insert": [vp, vp, vp, ll, ll, vp, vp, ci, vp, vp],
-        "crawl_yt_first_claim": [vp, vp, ll, ll, vp, vp, ci, vp, vp, vp],
-        "crawl_yt_uploads": [ll, vp, ll, ci, vp, vp, vp],
-        "crawl_yt_gen_meta_ids": [ll] * 4 + [vp] * 11 + [vp],
-        "crawl_yt_gen_fill_ids": [ll] * 3 + [vp] * 6 + [vp],
-        "crawl_yt_chan_lens": [ll, vp, ll, vp, vp, vp, vp],
-        # csrc/yt_snowball.hip
-        "crawl_yt_scan_count": [vp, vp, vp, ll, vp, vp],
-        "crawl_yt_scan_write": [vp, vp, vp, ll, vp, vp, vp],
-        "crawl_yt_cid_table_build": [ll, ll, vp, ci, vp, vp],
-        "crawl_yt_cid_lookup": [ll, vp, vp, ll, vp, ci, vp, vp],
-    }
-    for name, argtypes in sigs.items():
-        fn = getattr(lib, name)
-        fn.restype = ctypes.c_int
-        fn.argtypes = argtypes
-
-
-def _cur_stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _vp(t: Optional[torch.Tensor]):
-    return ctypes.c_void_p(None if t is None else t.data_ptr())
 
 
 def yt_search(index, prefixes: torch.Tensor) -> dict:
@@ -252,7 +237,6 @@ def yt_search(index, prefixes: torch.Tensor) -> dict:
     (bit 0 present, bit 1 rule-valid), and for rule-valid slots ``keys``
     (exact 64-bit id key), ``chan`` (channel index) and ``vcount`` (that
     channel's video_count)."""
-    lib = require_lib()
     dev = prefixes.device
     assert dev.type == "cuda" and prefixes.dtype == torch.uint8
     prefixes = prefixes.reshape(-1, 5).contiguous()
@@ -267,12 +251,8 @@ def yt_search(index, prefixes: torch.Tensor) -> dict:
         "chan": torch.empty(m, dtype=torch.int64, device=dev),
         "vcount": torch.empty(m, dtype=torch.int32, device=dev),
     }
-    rc = lib.crawl_yt_search(
-        index.seed, index.universe, _vp(prefixes), S, _vp(out["ids"]),
-        _vp(out["flags"]), _vp(out["keys"]), _vp(out["chan"]),
-        _vp(out["vcount"]), _cur_stream())
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_search failed: hip {rc}")
+    _call("crawl_yt_search", index.seed, index.universe, prefixes, S,
+          out["ids"], out["flags"], out["keys"], out["chan"], out["vcount"])
     return out
 
 
@@ -280,7 +260,6 @@ def yt_uploads(index, chans: torch.Tensor, limit: int):
     """SyntheticYouTubeIndex.channel_uploads for channel indices
     ``chans`` (int64[K] on the device): (ids uint8[K,29,11], counts
     int32[K]); slot k of row c is an upload iff k < counts[c]."""
-    lib = require_lib()
     dev = chans.device
     assert dev.type == "cuda" and chans.dtype == torch.int64
     chans = chans.contiguous()
@@ -289,10 +268,7 @@ def yt_uploads(index, chans: torch.Tensor, limit: int):
                       device=dev)
     counts = torch.empty(K, dtype=torch.int32, device=dev)
     limit = max(0, min(int(limit), YT_UPLOAD_SLOTS))
-    rc = lib.crawl_yt_uploads(index.seed, _vp(chans), K, limit, _vp(ids),
-                              _vp(counts), _cur_stream())
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_uploads failed: hip {rc}")
+    _call("crawl_yt_uploads", index.seed, chans, K, limit, ids, counts)
     return ids, counts
 
 
@@ -318,7 +294,7 @@ class YtFirstClaim:
         self.device = torch.device(device)
         self.grow = grow
         self.grown = 0
-        self._lib = require_lib()
+        require_lib()
         self._err = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._alloc(slots_log2)
         self._bound = 0  # upper bound on the distinct keys held
@@ -358,12 +334,8 @@ class YtFirstClaim:
         if log2 == self.slots_log2:
             return
         self._alloc(log2)
-        rc = self._lib.crawl_yt_claim_insert(
-            _vp(old_k), None, _vp(old_i), old_k.numel(), 0,
-            _vp(self.keys), _vp(self.min_idx), self.slots_log2,
-            _vp(self._err), _cur_stream())
-        if rc != 0:
-            raise RuntimeError(f"crawl_yt_claim_insert failed: hip {rc}")
+        _call("crawl_yt_claim_insert", old_k, None, old_i, old_k.numel(), 0,
+              self.keys, self.min_idx, self.slots_log2, self._err)
         self._check()
 
     def claim(self, keys: torch.Tensor, mask: Optional[torch.Tensor],
@@ -383,12 +355,8 @@ class YtFirstClaim:
         else:
             incoming = n
         self._reserve(incoming)
-        rc = self._lib.crawl_yt_first_claim(
-            _vp(keys), _vp(mask), n, int(base_idx), _vp(self.keys),
-            _vp(self.min_idx), self.slots_log2, _vp(first),
-            _vp(self._err), _cur_stream())
-        if rc != 0:
-            raise RuntimeError(f"crawl_yt_first_claim failed: hip {rc}")
+        _call("crawl_yt_first_claim", keys, mask, n, int(base_idx),
+              self.keys, self.min_idx, self.slots_log2, first, self._err)
         self._bound += incoming
         self._check()
         return first
@@ -408,7 +376,6 @@ def yt_scan_channel_ids(pool: torch.Tensor, text_off: torch.Tensor,
     int32[n])``: every match's absolute pool offset, in text order then
     match order, and the per-text match count. A match lies wholly inside
     its text; texts may be packed back to back."""
-    lib = require_lib()
     dev = pool.device
     assert dev.type == "cuda" and pool.dtype == torch.uint8
     assert text_off.dtype == torch.int64 and text_len.dtype == torch.int32
@@ -426,21 +393,15 @@ def yt_scan_channel_ids(pool: torch.Tensor, text_off: torch.Tensor,
            | (text_off + len64 > pool.numel())).any()
     if bool(bad.item()):
         raise ValueError("a text range lies outside the pool")
-    rc = lib.crawl_yt_scan_count(_vp(pool), _vp(text_off), _vp(text_len),
-                                 n, _vp(counts), _cur_stream())
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_scan_count failed: hip {rc}")
+    _call("crawl_yt_scan_count", pool, text_off, text_len, n, counts)
     c64 = counts.to(torch.int64)
     end = torch.cumsum(c64, 0)
     out_base = (end - c64).contiguous()
     total = int(end[-1].item())
     hit_off = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
-        rc = lib.crawl_yt_scan_write(_vp(pool), _vp(text_off),
-                                     _vp(text_len), n, _vp(out_base),
-                                     _vp(hit_off), _cur_stream())
-        if rc != 0:
-            raise RuntimeError(f"crawl_yt_scan_write failed: hip {rc}")
+        _call("crawl_yt_scan_write", pool, text_off, text_len, n, out_base,
+              hit_off)
     return hit_off, counts
 
 
@@ -467,17 +428,12 @@ class YtChannelReverseMap:
             while (1 << slots_log2) < 2 * self.universe:
                 slots_log2 += 1
         self.slots_log2 = int(slots_log2)
-        self._lib = require_lib()
         with torch.cuda.device(self.device):
             self.table = torch.full((1 << self.slots_log2,), -1,
                                     dtype=torch.int64, device=self.device)
             err = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = self._lib.crawl_yt_cid_table_build(
-                self.seed, self.universe, _vp(self.table), self.slots_log2,
-                _vp(err), _cur_stream())
-            if rc != 0:
-                raise RuntimeError(
-                    f"crawl_yt_cid_table_build failed: hip {rc}")
+            _call("crawl_yt_cid_table_build", self.seed, self.universe,
+                  self.table, self.slots_log2, err)
             e = int(err.item())
         if e:
             raise YtClaimTableError(
@@ -499,29 +455,9 @@ class YtChannelReverseMap:
         bad = ((hit_off < 0) | (hit_off + YT_CID_LEN > pool.numel())).any()
         if bool(bad.item()):
             raise ValueError("an id offset lies outside the pool")
-        rc = self._lib.crawl_yt_cid_lookup(
-            self.seed, _vp(pool), _vp(hit_off), m, _vp(self.table),
-            self.slots_log2, _vp(out), _cur_stream())
-        if rc != 0:
-            raise RuntimeError(f"crawl_yt_cid_lookup failed: hip {rc}")
+        _call("crawl_yt_cid_lookup", self.seed, pool, hit_off, m, self.table,
+              self.slots_log2, out)
         return out
-
-
-def _bind_aux(lib):
-    lib.crawl_channel_stats.restype = ctypes.c_int
-    lib.crawl_channel_stats.argtypes = [ctypes.c_void_p] * 4 + [
-        ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + [
-        ctypes.c_void_p]
-    lib.crawl_reservoir_sample.restype = ctypes.c_int
-    lib.crawl_reservoir_sample.argtypes = [
-        ctypes.c_long, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_html_classify.restype = ctypes.c_int
-    lib.crawl_html_classify.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
-    ]
 
 
 def channel_stats(batch: B.MessageBatch, line_len=None):
@@ -529,7 +465,6 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
     GetTotalChannelViews etc. -> one workgroup per channel segment).
     Returns dict of device tensors: views/forwards/replies int64[K],
     posts int32[K], totals int64[4] (views,forwards,replies,posts)."""
-    lib = require_lib()
     dev = batch.device
     K = batch.n_channels
     P = batch.n // K
@@ -542,40 +477,21 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
         "totals": torch.zeros(4, dtype=torch.int64, device=dev),
     }
     m = batch.meta
-    rc = lib.crawl_channel_stats(
-        ctypes.c_void_p(m["views"].data_ptr()),
-        ctypes.c_void_p(m["forwards"].data_ptr()),
-        ctypes.c_void_p(m["reply_count"].data_ptr()),
-        ctypes.c_void_p(line_len.data_ptr()) if line_len is not None
-        else None,
-        P, K,
-        ctypes.c_void_p(out["views"].data_ptr()),
-        ctypes.c_void_p(out["forwards"].data_ptr()),
-        ctypes.c_void_p(out["replies"].data_ptr()),
-        ctypes.c_void_p(out["posts"].data_ptr()),
-        ctypes.c_void_p(out["totals"].data_ptr()),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream),
-    )
-    if rc != 0:
-        raise RuntimeError(f"crawl_channel_stats failed: hip {rc}")
+    _call("crawl_channel_stats", m["views"], m["forwards"], m["reply_count"],
+          line_len, P, K, out["views"], out["forwards"], out["replies"],
+          out["posts"], out["totals"])
     return out
 
 
 def reservoir_sample(batch: B.MessageBatch, k: int, seed: int = 0):
     """Per-channel uniform sample without replacement (SURVEY §2.6
     Fisher-Yates row). Returns int32[K, k] global row indices (device)."""
-    lib = require_lib()
     dev = batch.device
     K = batch.n_channels
     P = batch.n // K
     out = torch.zeros((K, k), dtype=torch.int32, device=dev)
-    rc = lib.crawl_reservoir_sample(
-        seed, P, K, k, ctypes.c_void_p(out.data_ptr()),
-        min(max(1, (K + 3) // 4), 8192),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream),
-    )
-    if rc != 0:
-        raise RuntimeError(f"crawl_reservoir_sample failed: hip {rc}")
+    _call("crawl_reservoir_sample", seed, P, K, k, out,
+          min(max(1, (K + 3) // 4), 8192))
     return out
 
 
@@ -609,7 +525,6 @@ def html_classify(docs, device="cuda:0"):
     """Batch t.me HTML classification on GPU (oracle:
     engine.htmlvalidator.parse_channel_html). docs: list[bytes].
     Returns list of (status, reason) strings."""
-    lib = require_lib()
     dev = torch.device(device)
     n = len(docs)
     blob = b"".join(docs) or b"\0"
@@ -624,74 +539,12 @@ def html_classify(docs, device="cuda:0"):
     doc_len = torch.tensor(lens, dtype=torch.int32, device=dev)
     status = torch.zeros(n, dtype=torch.int32, device=dev)
     reason = torch.zeros(n, dtype=torch.int32, device=dev)
-    rc = lib.crawl_html_classify(
-        ctypes.c_void_p(pool.data_ptr()),
-        ctypes.c_void_p(doc_off.data_ptr()),
-        ctypes.c_void_p(doc_len.data_ptr()), n,
-        ctypes.c_void_p(status.data_ptr()),
-        ctypes.c_void_p(reason.data_ptr()),
-        min(max(1, (n + 3) // 4), 8192),
-        ctypes.c_void_p(torch.cuda.current_stream().cuda_stream),
-    )
-    if rc != 0:
-        raise RuntimeError(f"crawl_html_classify failed: hip {rc}")
+    _call("crawl_html_classify", pool, doc_off, doc_len, n, status, reason,
+          min(max(1, (n + 3) // 4), 8192))
     st = status.cpu().numpy()
     rs = reason.cpu().numpy()
     return [(_HTML_STATUS[int(st[i])], _HTML_REASON[int(rs[i])])
             for i in range(n)]
-
-
-def _bind_dedup(lib):
-    lib.crawl_claim_links.restype = ctypes.c_int
-    lib.crawl_claim_links.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_bloom_update.restype = ctypes.c_int
-    lib.crawl_bloom_update.argtypes = [
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-        ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p,
-    ]
-    lib.crawl_insert_hashes.restype = ctypes.c_int
-    lib.crawl_insert_hashes.argtypes = [
-        ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_longlong,
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-
-
-def _bind_feedgen(lib):
-    lib.crawl_feed_meta.restype = ctypes.c_int
-    lib.crawl_feed_meta.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.crawl_feed_fill.restype = ctypes.c_int
-    lib.crawl_feed_fill.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int,
-        ctypes.c_void_p,
-    ]
-    lib.crawl_feed_comments.restype = ctypes.c_int
-    lib.crawl_feed_comments.argtypes = [
-        ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_long),
-        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p,
-        ctypes.c_long, ctypes.c_long, ctypes.POINTER(ctypes.c_void_p),
-        ctypes.c_int, ctypes.c_void_p,
-    ]
-
-
-def require_lib():
-    """On a GPU host, a missing/failed extension is an ERROR, not a fallback."""
-    if not lib_available():
-        raise RuntimeError(
-            "libcrawlhip.so not built — run __graft_entry__.build() "
-            "(hipcc --offload-arch=gfx950) before GPU execution; the Python "
-            "golden path is not a substitute on GPU hosts"
-        )
-    return load_lib()
 
 
 # Emoji / content-type constant tables shipped to the device once.
@@ -982,10 +835,6 @@ def parse_encode(
 
     if grid <= 0:
         grid = min((n + 3) // 4, 8192)
-    stream_ptr = ctypes.c_void_p(
-        torch.cuda.current_stream().cuda_stream if stream is None
-        else stream.cuda_stream
-    )
 
     stage_need = None
     if (not single_pass and not os.environ.get("CRAWL_LDS_WRITE")
@@ -1001,14 +850,8 @@ def parse_encode(
         if _poison is not None:
             scratch.fill_(_poison)
         overflow = torch.zeros(1, dtype=torch.int32, device=dev)
-        rc = lib.crawl_write_scratch(
-            batch_ptrs, scalars, link_ptrs,
-            ctypes.c_void_p(scratch.data_ptr()), stride,
-            ctypes.c_void_p(line_len.data_ptr()),
-            ctypes.c_void_p(overflow.data_ptr()), grid, stream_ptr,
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_write_scratch failed: hip error {rc}")
+        _call("crawl_write_scratch", batch_ptrs, scalars, link_ptrs, scratch,
+              stride, line_len, overflow, grid, stream=stream)
         line_off = torch.zeros(n, dtype=torch.int64, device=dev)
         torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
         total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
@@ -1019,23 +862,11 @@ def parse_encode(
                 "stride bound is unsound for this batch"
             )
         out, raw = _alloc_out(total, dev, _poison, _guard)
-        rc = lib.crawl_compact(
-            ctypes.c_void_p(scratch.data_ptr()), stride,
-            ctypes.c_void_p(line_off.data_ptr()),
-            ctypes.c_void_p(line_len.data_ptr()),
-            ctypes.c_void_p(out.data_ptr()), n, grid, stream_ptr,
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_compact failed: hip error {rc}")
+        _call("crawl_compact", scratch, stride, line_off, line_len, out, n,
+              grid, stream=stream)
     else:
-        rc = lib.crawl_measure_extract(
-            batch_ptrs, scalars, link_ptrs,
-            ctypes.c_void_p(line_len.data_ptr()), grid, stream_ptr,
-        )
-        if rc != 0:
-            raise RuntimeError(
-                f"crawl_measure_extract launch failed: hip error {rc}"
-            )
+        _call("crawl_measure_extract", batch_ptrs, scalars, link_ptrs,
+              line_len, grid, stream=stream)
         line_off = torch.zeros(n, dtype=torch.int64, device=dev)
         torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
         total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
@@ -1045,27 +876,14 @@ def parse_encode(
             # outlinks + per-batch tables go through LDS so in-line
             # loads never wait the store FIFO (profiles/
             # r02_valu_diet.md); host verified everything fits
-            rc = lib.crawl_write_staged(
-                batch_ptrs, scalars, link_ptrs,
-                ctypes.c_void_p(line_off.data_ptr()),
-                ctypes.c_void_p(line_len.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()),
-                tables["emoji_off"].numel(),
-                tables["emoji_pool"].numel(),
-                tables["ctname_off"].numel(),
-                tables["ctname_pool"].numel(), grid, stream_ptr,
-            )
+            _call("crawl_write_staged", batch_ptrs, scalars, link_ptrs,
+                  line_off, line_len, out, tables["emoji_off"].numel(),
+                  tables["emoji_pool"].numel(), tables["ctname_off"].numel(),
+                  tables["ctname_pool"].numel(), grid, stream=stream)
         else:
-            write_fn = (lib.crawl_write_lds if writer == "lds"
-                        else lib.crawl_write)
-            rc = write_fn(
-                batch_ptrs, scalars, link_ptrs,
-                ctypes.c_void_p(line_off.data_ptr()),
-                ctypes.c_void_p(line_len.data_ptr()),
-                ctypes.c_void_p(out.data_ptr()), grid, stream_ptr,
-            )
-        if rc != 0:
-            raise RuntimeError(f"crawl_write launch failed: hip error {rc}")
+            _call("crawl_write_lds" if writer == "lds" else "crawl_write",
+                  batch_ptrs, scalars, link_ptrs, line_off, line_len, out,
+                  grid, stream=stream)
 
     return EncodeResult(
         out=out, line_off=line_off, line_len=line_len,
@@ -1094,9 +912,6 @@ class SeenSet:
         self._n_new = torch.zeros(1, dtype=torch.int32, device=device)
         self.lib = require_lib()
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     def claim(self, res: EncodeResult) -> torch.Tensor:
         """Claim every extracted link; returns new_mask uint8[N, MAX_LINKS].
 
@@ -1109,28 +924,10 @@ class SeenSet:
         )
         self._n_new.zero_()
         grid = min((n * MAX_LINKS + 255) // 256, 4096)
-        rc = self.lib.crawl_claim_links(
-            ctypes.c_void_p(res.link_hash.data_ptr()),
-            ctypes.c_void_p(res.link_cnt.data_ptr()),
-            n, MAX_LINKS,
-            ctypes.c_void_p(self.table.data_ptr()),
-            ctypes.c_longlong(self.slots),
-            ctypes.c_void_p(new_mask.data_ptr()),
-            ctypes.c_void_p(self._n_new.data_ptr()),
-            grid, self._stream(),
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_claim_links failed: hip error {rc}")
-        rc = self.lib.crawl_bloom_update(
-            ctypes.c_void_p(res.link_hash.data_ptr()),
-            ctypes.c_void_p(res.link_cnt.data_ptr()),
-            n, MAX_LINKS,
-            ctypes.c_void_p(self.bloom.data_ptr()),
-            ctypes.c_longlong(self.bloom_bits),
-            grid, self._stream(),
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_bloom_update failed: hip error {rc}")
+        _call("crawl_claim_links", res.link_hash, res.link_cnt, n, MAX_LINKS,
+              self.table, self.slots, new_mask, self._n_new, grid)
+        _call("crawl_bloom_update", res.link_hash, res.link_cnt, n, MAX_LINKS,
+              self.bloom, self.bloom_bits, grid)
         return new_mask
 
     def new_count(self) -> int:
@@ -1149,20 +946,9 @@ class SeenSet:
                                  device=self.device)
         cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
         grid = min((cap + 255) // 256, 4096)
-        rc = self.lib.crawl_claim_compact(
-            ctypes.c_void_p(new_mask.data_ptr()),
-            ctypes.c_void_p(res.link_name.data_ptr()),
-            ctypes.c_void_p(res.link_len.data_ptr()),
-            ctypes.c_void_p(res.link_hash.data_ptr()),
-            n, MAX_LINKS,
-            ctypes.c_void_p(out_names.data_ptr()),
-            ctypes.c_void_p(out_hashes.data_ptr()),
-            ctypes.c_void_p(cursor.data_ptr()),
-            ctypes.c_uint(cap), grid, self._stream(),
-        )
-        if rc != 0:
-            raise RuntimeError(
-                f"crawl_claim_compact failed: hip error {rc}")
+        _call("crawl_claim_compact", new_mask, res.link_name, res.link_len,
+              res.link_hash, n, MAX_LINKS, out_names, out_hashes, cursor, cap,
+              grid)
         m = int(cursor.item())  # syncs the stream
         return out_names[:m], out_hashes[:m]
 
@@ -1197,13 +983,7 @@ class SeenSet:
         if n == 0:
             return
         grid = min((n + 255) // 256, 4096)
-        rc = self.lib.crawl_insert_hashes(
-            ctypes.c_void_p(hashes.data_ptr()), ctypes.c_long(n),
-            ctypes.c_void_p(self.table.data_ptr()),
-            ctypes.c_longlong(self.slots), grid, self._stream(),
-        )
-        if rc != 0:
-            raise RuntimeError(f"crawl_insert_hashes failed: hip error {rc}")
+        _call("crawl_insert_hashes", hashes, n, self.table, self.slots, grid)
 
 
 def fnv1a64(data: bytes) -> int:

@@ -458,140 +458,37 @@ def build_corpus_fast(index: SyntheticYouTubeIndex, n_videos: int,
     )
 
 
+# ---------- device builders (csrc/yt_feedgen.hip) ----------
+
+def yt_ids_from_index_device(index: SyntheticYouTubeIndex, i0: int, n: int,
+                             device) -> torch.Tensor:
+    """The ids of rows ``i0 .. i0+n-1`` of :func:`build_corpus`'s prefix
+    walk, uint8[n,11] on the device: the prefix is the base-26 digits of
+    the row index (it wraps at 26**5) and ``k = i % 7``."""
+    from ..ops import gpu as _g
+
+    ids = torch.empty((n, 11), dtype=torch.uint8, device=device)
+    if n:
+        _g._call("crawl_yt_gen_ids", index.seed, i0, n, ids)
+    return ids
+
+
 def build_corpus_device(index: SyntheticYouTubeIndex, n_videos: int,
                         device, crawl_label: str = "",
                         i0: int = 0) -> YouTubeBatch:
-    """GPU-resident corpus generation (csrc/yt_feedgen.hip) — the
-    YouTube half of the device synthetic-API engine. Byte-identical to
-    build_corpus_fast (GPU test pins it); generation never leaves HBM."""
-    import ctypes
+    """GPU-resident corpus generation — the YouTube half of the device
+    synthetic-API engine: the prefix walk's ids, then
+    :func:`build_batch_from_ids_device`. Byte-identical to
+    build_corpus_fast (GPU test pins it); generation never leaves HBM.
 
-    from ..feed.synth import _splitmix64
-    from ..ops import gpu as _g
-
-    lib = _g.require_lib()
-    dev = torch.device(device)
-    n = n_videos
-    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-    z64 = lambda m, dt_: torch.empty(m, dtype=dt_, device=dev)
-    vid_pool = z64(n * 11, torch.uint8)
-    published = z64(n, torch.int64)
-    views = z64(n, torch.int64)
-    likes = z64(n, torch.int32)
-    comments = z64(n, torch.int32)
-    duration_s = z64(n, torch.int32)
-    lang = z64(n, torch.int32)
-    n_chan = z64(n, torch.int64)
-    topic = z64(n, torch.int32)
-    tnum = z64(n, torch.int32)
-    desc_len = z64(n, torch.int32)
-    cv = ctypes.c_void_p
-    rc = lib.crawl_yt_gen_meta(
-        index.seed, index.universe, index.base_date, n, i0,
-        cv(vid_pool.data_ptr()), cv(published.data_ptr()),
-        cv(views.data_ptr()), cv(likes.data_ptr()),
-        cv(comments.data_ptr()), cv(duration_s.data_ptr()),
-        cv(lang.data_ptr()), cv(n_chan.data_ptr()),
-        cv(topic.data_ptr()), cv(tnum.data_ptr()),
-        cv(desc_len.data_ptr()), stream)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_meta failed: hip {rc}")
-
-    # layout: [vid n*11 | title n*27 | desc var | channel region]
-    vid_off = (torch.arange(n, dtype=torch.int64, device=dev) * 11)
-    title_off = n * 11 + torch.arange(n, dtype=torch.int64,
-                                      device=dev) * 27
-    desc_base = n * 11 + n * 27
-    dl64 = desc_len.to(torch.int64)
-    desc_off = torch.zeros(n, dtype=torch.int64, device=dev)
-    if n > 1:
-        torch.cumsum(dl64[:-1], 0, out=desc_off[1:])
-    desc_off += desc_base
-    desc_total = int(desc_base + dl64.sum().item())
-
-    # channel table in FIRST-APPEARANCE order
-    uniq, inverse = torch.unique(n_chan, sorted=True,
-                                 return_inverse=True)
-    K = uniq.numel()
-    first = torch.full((K,), n, dtype=torch.int64, device=dev)
-    first.scatter_reduce_(0, inverse,
-                          torch.arange(n, dtype=torch.int64, device=dev),
-                          reduce="amin")
-    order = torch.argsort(first)
-    rank = torch.empty_like(order)
-    rank[order] = torch.arange(K, dtype=torch.int64, device=dev)
-    channel_idx = rank[inverse].to(torch.int32)
-    chan_ns = uniq[order]
-
-    # channel string lengths (digits via comparisons; hc on host numpy
-    # for the country flag — torch lacks uint64 bit ops)
-    digs = torch.ones(K, dtype=torch.int64, device=dev)
-    p10 = 10
-    for _ in range(18):
-        digs += (chan_ns >= p10).to(torch.int64)
-        p10 *= 10
-    title_len_ch = 21 + digs
-    desc_len_ch = 8 + digs + 36
-    ns_host = chan_ns.cpu().numpy().astype(np.uint64)
-    a = np.uint64(index.seed ^ 0xC0FFEE)
-    for chf in "chanmeta":
-        a = _splitmix64(np.asarray(a ^ np.uint64(ord(chf))))
-    hc = _splitmix64(np.full(K, a, dtype=np.uint64) ^ ns_host)
-    country_len_np = np.where(hc % np.uint64(3) == 0, 2, 0)
-    country_len = torch.from_numpy(
-        country_len_np.astype(np.int64)).to(dev)
-    block = 24 + title_len_ch + desc_len_ch + country_len
-    ch_base = torch.zeros(K, dtype=torch.int64, device=dev)
-    if K > 1:
-        torch.cumsum(block[:-1], 0, out=ch_base[1:])
-    ch_base += desc_total
-    id_off = ch_base
-    t_off = id_off + 24
-    d_off = t_off + title_len_ch
-    c_off = d_off + desc_len_ch
-    total = int(desc_total + block.sum().item())
-
-    pool = torch.zeros(total, dtype=torch.uint8, device=dev)
-    rc = lib.crawl_yt_gen_fill(
-        index.seed, index.universe, index.base_date, n, i0,
-        cv(vid_pool.data_ptr()), cv(topic.data_ptr()),
-        cv(tnum.data_ptr()), cv(title_off.data_ptr()),
-        cv(desc_off.data_ptr()), cv(pool.data_ptr()), stream)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_fill failed: hip {rc}")
-    subs = z64(K, torch.int64)
-    videos_t = z64(K, torch.int32)
-    ch_views = z64(K, torch.int64)
-    ch_published = z64(K, torch.int64)
-    rc = lib.crawl_yt_gen_channels(
-        index.seed, index.universe, index.base_date,
-        cv(chan_ns.data_ptr()), K, cv(id_off.data_ptr()),
-        cv(t_off.data_ptr()), cv(d_off.data_ptr()),
-        cv(c_off.data_ptr()), cv(subs.data_ptr()),
-        cv(videos_t.data_ptr()), cv(ch_views.data_ptr()),
-        cv(ch_published.data_ptr()), cv(pool.data_ptr()), stream)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_channels failed: hip {rc}")
-
-    return YouTubeBatch(
-        n=n, vid_off=vid_off.to(torch.int32), channel_idx=channel_idx,
-        published=published, views=views, likes=likes,
-        comments=comments, duration_s=duration_s, lang=lang,
-        title_off=title_off, title_len=torch.full(
-            (n,), 27, dtype=torch.int32, device=dev),
-        desc_off=desc_off, desc_len=desc_len, pool=pool,
-        n_channels=int(K),
-        ch_id_off=id_off.to(torch.int32),
-        ch_title_off=t_off.to(torch.int32),
-        ch_title_len=title_len_ch.to(torch.int32),
-        ch_desc_off=d_off.to(torch.int32),
-        ch_desc_len=desc_len_ch.to(torch.int32),
-        ch_subs=subs, ch_videos=videos_t, ch_views=ch_views,
-        ch_country_off=c_off.to(torch.int32),
-        ch_country_len=country_len.to(torch.int32),
-        ch_published=ch_published,
-        crawl_label=crawl_label,
-    )
+    Sharing the id-driven builder decides two edge cases: ``n_videos ==
+    0`` gives an empty batch (no launch, so no invalid-configuration
+    RuntimeError), and a pool of 2**31 bytes or more raises ValueError
+    where the int32 offsets would wrap. Every other batch is field for
+    field what a builder walking the prefixes itself would return: the
+    same pool layout, the same first-appearance channel order."""
+    ids = yt_ids_from_index_device(index, i0, n_videos, device)
+    return build_batch_from_ids_device(index, ids, device, crawl_label)
 
 
 def yt_meta_from_ids_device(index: SyntheticYouTubeIndex,
@@ -601,7 +498,6 @@ def yt_meta_from_ids_device(index: SyntheticYouTubeIndex,
     ``vidmeta`` hash. ``n_chan`` is the channel index."""
     from ..ops import gpu as _g
 
-    lib = _g.require_lib()
     dev = ids_u8.device
     assert dev.type == "cuda" and ids_u8.dtype == torch.uint8
     vid_pool = ids_u8.reshape(-1, 11).contiguous()
@@ -613,15 +509,32 @@ def yt_meta_from_ids_device(index: SyntheticYouTubeIndex,
          "lang": e(torch.int32), "n_chan": e(torch.int64),
          "topic": e(torch.int32), "tnum": e(torch.int32),
          "desc_len": e(torch.int32)}
-    p = _g._vp
-    rc = lib.crawl_yt_gen_meta_ids(
-        index.seed, index.universe, index.base_date, n, p(vid_pool),
-        p(m["published"]), p(m["views"]), p(m["likes"]), p(m["comments"]),
-        p(m["duration_s"]), p(m["lang"]), p(m["n_chan"]), p(m["topic"]),
-        p(m["tnum"]), p(m["desc_len"]), _g._cur_stream())
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_meta_ids failed: hip {rc}")
+    _g._call("crawl_yt_gen_meta", index.seed, index.universe,
+             index.base_date, n, vid_pool, m["published"], m["views"],
+             m["likes"], m["comments"], m["duration_s"], m["lang"],
+             m["n_chan"], m["topic"], m["tnum"], m["desc_len"])
     return m
+
+
+def _video_region(desc_len: torch.Tensor):
+    """The video region ``[vid n*11 | title n*27 | desc var]`` that opens
+    a generated pool, from desc_len int32[n]: ``(vid_off, title_off,
+    desc_off, end)``, int64[n] offsets and the region's size in bytes."""
+    n = desc_len.numel()
+    ar = torch.arange(n, dtype=torch.int64, device=desc_len.device)
+    desc_base = n * (11 + 27)
+    dl64 = desc_len.to(torch.int64)
+    desc_off = torch.cumsum(dl64, 0) - dl64 + desc_base
+    return (ar * 11, n * 11 + ar * 27, desc_off,
+            int(desc_base + dl64.sum().item()))
+
+
+def _fill_videos(index, m: dict, title_off, desc_off, pool) -> None:
+    from ..ops import gpu as _g
+
+    _g._call("crawl_yt_gen_fill", index.seed, index.universe,
+             m["vid_pool"].shape[0], m["vid_pool"], m["topic"], m["tnum"],
+             title_off, desc_off, pool)
 
 
 def yt_descriptions_from_ids_device(index: SyntheticYouTubeIndex,
@@ -631,63 +544,41 @@ def yt_descriptions_from_ids_device(index: SyntheticYouTubeIndex,
     int32[n])``. The lighter sibling of :func:`build_batch_from_ids_device`
     for callers that only read the texts: the same meta and fill kernels
     and the same ``[vid | title | desc]`` layout, with no channel table."""
-    from ..ops import gpu as _g
-
-    lib = _g.require_lib()
-    dev = ids_u8.device
     m = yt_meta_from_ids_device(index, ids_u8)
-    vid_pool, desc_len = m["vid_pool"], m["desc_len"]
-    n = vid_pool.shape[0]
-    p = _g._vp
-    ar = torch.arange(n, dtype=torch.int64, device=dev)
-    title_off = n * 11 + ar * 27
-    dl64 = desc_len.to(torch.int64)
-    desc_off = (torch.cumsum(dl64, 0) - dl64 + n * (11 + 27)).contiguous()
-    total = n * (11 + 27) + (int(dl64.sum().item()) if n else 0)
-    pool = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
-    rc = lib.crawl_yt_gen_fill_ids(
-        index.seed, index.universe, n, p(vid_pool), p(m["topic"]),
-        p(m["tnum"]), p(title_off), p(desc_off), p(pool), _g._cur_stream())
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_fill_ids failed: hip {rc}")
-    return pool, desc_off, desc_len
+    _, title_off, desc_off, total = _video_region(m["desc_len"])
+    pool = torch.zeros(max(total, 1), dtype=torch.uint8,
+                       device=ids_u8.device)
+    _fill_videos(index, m, title_off, desc_off, pool)
+    return pool, desc_off, m["desc_len"]
 
 
 def build_batch_from_ids_device(index: SyntheticYouTubeIndex,
                                 ids_u8: torch.Tensor, device,
                                 crawl_label: str = "") -> YouTubeBatch:
-    """Device batch for the videos NAMED by ``ids_u8`` (uint8[n,11]):
-    the id-driven sibling of :func:`build_corpus_device`, for search
-    hits and channel uploads. Equal, through the encoder, to
+    """Device batch for the videos NAMED by ``ids_u8`` (uint8[n,11]): the
+    one device builder, for the prefix walk (:func:`build_corpus_device`),
+    search hits and channel uploads. Equal, through the encoder, to
     ``pack_videos([index.video(id) ...])`` with a first-appearance
-    channel table. Unlike build_corpus_device the channel table's string
-    lengths come from a kernel, so nothing returns to the host but the
-    two pool-size scalars. Callers keep n <= 1M so the int32 pool
-    offsets hold."""
+    channel table. Nothing returns to the host but the two pool-size
+    scalars. A pool past the int32 offsets raises ValueError: callers
+    chunk the ids (1M videos fit)."""
     from ..ops import gpu as _g
 
-    lib = _g.require_lib()
     dev = torch.device(device)
-    ids_u8 = ids_u8.to(dev)
-    m = yt_meta_from_ids_device(index, ids_u8)
-    vid_pool, desc_len, n_chan = m["vid_pool"], m["desc_len"], m["n_chan"]
-    n = vid_pool.shape[0]
-    p, stream = _g._vp, _g._cur_stream()
-    ar = torch.arange(n, dtype=torch.int64, device=dev)
+    m = yt_meta_from_ids_device(index, ids_u8.to(dev))
+    desc_len, n_chan = m["desc_len"], m["n_chan"]
+    n = desc_len.numel()
 
     # layout: [vid n*11 | title n*27 | desc var | channel region]
-    vid_off = ar * 11
-    title_off = n * 11 + ar * 27
-    desc_base = n * 11 + n * 27
-    dl64 = desc_len.to(torch.int64)
-    desc_off = torch.cumsum(dl64, 0) - dl64 + desc_base
-    desc_total = int(desc_base + dl64.sum().item())
+    vid_off, title_off, desc_off, desc_total = _video_region(desc_len)
 
     # channel table in FIRST-APPEARANCE order
     uniq, inverse = torch.unique(n_chan, sorted=True, return_inverse=True)
     K = uniq.numel()
     first = torch.full((K,), n, dtype=torch.int64, device=dev)
-    first.scatter_reduce_(0, inverse, ar, reduce="amin")
+    first.scatter_reduce_(
+        0, inverse, torch.arange(n, dtype=torch.int64, device=dev),
+        reduce="amin")
     order = torch.argsort(first)
     rank = torch.empty_like(order)
     rank[order] = torch.arange(K, dtype=torch.int64, device=dev)
@@ -697,11 +588,8 @@ def build_batch_from_ids_device(index: SyntheticYouTubeIndex,
     title_len_ch = torch.empty(K, dtype=torch.int64, device=dev)
     desc_len_ch = torch.empty(K, dtype=torch.int64, device=dev)
     country_len = torch.empty(K, dtype=torch.int64, device=dev)
-    rc = lib.crawl_yt_chan_lens(index.seed, p(chan_ns), K,
-                                p(title_len_ch), p(desc_len_ch),
-                                p(country_len), stream)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_chan_lens failed: hip {rc}")
+    _g._call("crawl_yt_chan_lens", index.seed, chan_ns, K, title_len_ch,
+             desc_len_ch, country_len)
     block = 24 + title_len_ch + desc_len_ch + country_len
     id_off = torch.cumsum(block, 0) - block + desc_total
     t_off = id_off + 24
@@ -714,21 +602,13 @@ def build_batch_from_ids_device(index: SyntheticYouTubeIndex,
             "chunk the ids")
 
     pool = torch.zeros(max(total, 1), dtype=torch.uint8, device=dev)
-    rc = lib.crawl_yt_gen_fill_ids(
-        index.seed, index.universe, n, p(vid_pool), p(m["topic"]),
-        p(m["tnum"]), p(title_off), p(desc_off), p(pool), stream)
-    if rc != 0:
-        raise RuntimeError(f"crawl_yt_gen_fill_ids failed: hip {rc}")
+    _fill_videos(index, m, title_off, desc_off, pool)
     z = lambda dt_: torch.empty(K, dtype=dt_, device=dev)
     subs, videos_t = z(torch.int64), z(torch.int32)
     ch_views, ch_published = z(torch.int64), z(torch.int64)
-    if K:
-        rc = lib.crawl_yt_gen_channels(
-            index.seed, index.universe, index.base_date, p(chan_ns), K,
-            p(id_off), p(t_off), p(d_off), p(c_off), p(subs),
-            p(videos_t), p(ch_views), p(ch_published), p(pool), stream)
-        if rc != 0:
-            raise RuntimeError(f"crawl_yt_gen_channels failed: hip {rc}")
+    _g._call("crawl_yt_gen_channels", index.seed, index.base_date, chan_ns,
+             K, id_off, t_off, d_off, c_off, subs, videos_t, ch_views,
+             ch_published, pool)
 
     i32 = lambda t_: t_.to(torch.int32)
     return YouTubeBatch(

@@ -177,3 +177,53 @@ def test_device_corpus_from_i0(gpu_mod, universe, i0):
     assert encode_yt_batch(dev.to("cpu"), now=C.NOW) == want
     # ... and through the device encoder
     _check(_run(gpu_mod, dev), want, f"device i0={i0} u={universe}")
+
+
+def _walk_ids(idx, i0, n):
+    """build_corpus's walk: base-26 prefix of i, video_id(prefix, i % 7)."""
+    import string
+
+    ids = []
+    for i in range(i0, i0 + n):
+        p, v = "", i
+        for _ in range(5):
+            p = string.ascii_lowercase[v % 26] + p
+            v //= 26
+        ids.append(idx.video_id(p, i % 7))
+    return ids
+
+
+@pytest.mark.parametrize("i0,n", [(0, 1), (0, 257), (WRAP - 32, 64),
+                                  (123_456_789, 3)])
+def test_ids_from_index_device(gpu_mod, i0, n):
+    """The id kernel against the Python walk: one id, one thread past a
+    full block, across the 26**5 wrap, and an i0 far past it."""
+    from crawler_amd.youtube.batch import yt_ids_from_index_device
+
+    idx = SyntheticYouTubeIndex(seed=17, universe_channels=63)
+    ids = yt_ids_from_index_device(idx, i0, n, "cuda:0")
+    torch.cuda.synchronize()
+    assert tuple(ids.shape) == (n, 11) and ids.dtype == torch.uint8
+    got = [bytes(r).decode() for r in ids.cpu().numpy()]
+    assert got == _walk_ids(idx, i0, n)
+
+
+def test_ids_from_index_device_empty(gpu_mod):
+    from crawler_amd.youtube.batch import yt_ids_from_index_device
+
+    idx = SyntheticYouTubeIndex(seed=17, universe_channels=63)
+    ids = yt_ids_from_index_device(idx, 5, 0, "cuda:0")
+    assert tuple(ids.shape) == (0, 11) and ids.dtype == torch.uint8
+    assert ids.device.type == "cuda"
+
+
+def test_device_corpus_empty(gpu_mod):
+    """Zero videos: an empty batch, through the oracle and the encoder."""
+    idx = SyntheticYouTubeIndex(seed=17, universe_channels=63)
+    b = build_corpus_device(idx, 0, "cuda:0")
+    torch.cuda.synchronize()
+    assert b.n == 0 and b.n_channels == 0
+    assert encode_yt_batch(b.to("cpu")) == []
+    out, line_off, line_len = gpu_mod.yt_parse_encode(b)
+    torch.cuda.synchronize()
+    assert out.numel() == 0 and line_len.numel() == 0

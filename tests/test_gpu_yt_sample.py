@@ -1,5 +1,5 @@
 """yt_sample.hip kernels vs the synthetic index's own Python: search,
-first-claim, uploads, and the id-driven batch builder."""
+first-claim, uploads, and the batch builder (yt_feedgen.hip) on their ids."""
 import datetime as dt
 import random
 
