@@ -255,9 +255,13 @@ class FeedConfig:
 class SyntheticFeed:
     """Deterministic channel/history generator in packed-batch form."""
 
-    def __init__(self, cfg: Optional[FeedConfig] = None):
+    def __init__(self, cfg: Optional[FeedConfig] = None,
+                 templates: Optional[List[Template]] = None):
+        """``templates`` replaces the standard template set (they are
+        compiled here)."""
         self.cfg = cfg or FeedConfig()
-        self.templates = default_templates()
+        self.templates = (default_templates() if templates is None
+                          else [_compile(t) for t in templates])
         w = np.array([t.weight for t in self.templates])
         self._cdf = np.cumsum(w) / w.sum()
         # Precompute template arrays
@@ -279,6 +283,15 @@ class SyntheticFeed:
         self._n_slots = np.array([len(t.slot_positions)
                                   for t in self.templates])
         self._comment_bytes = [c.encode("utf-8") for c in COMMENT_TEXTS]
+
+    def _check_comment_cfg(self):
+        """A post with comments has 1..max_comments_per_post of them, so a
+        non-zero rate needs room for at least one."""
+        if self.cfg.comment_rate > 0 and self.cfg.max_comments_per_post < 1:
+            raise ValueError(
+                "max_comments_per_post must be at least 1 when "
+                "comment_rate is non-zero"
+            )
 
     # ---- device-side generation (csrc/feedgen.hip) ----
 
@@ -362,18 +375,25 @@ class SyntheticFeed:
         P = posts_per_channel or cfg.posts_per_channel
         K = len(channel_ids)
         N = K * P
+        self._check_comment_cfg()
         permille = cfg.comment_rate * 1000
-        assert permille == int(permille), (
-            "comment_rate must be an integer number of permille for the "
-            "device generator"
-        )
+        if permille != int(permille):
+            raise ValueError(
+                "comment_rate must be an integer number of permille for the "
+                "device generator"
+            )
+        if K == 0:
+            # nothing to launch (a grid of 0 blocks is invalid): the empty
+            # batch has the CPU builder's fields and dtypes
+            return self.build_batch(
+                np.zeros(0, dtype=np.int64), P).to(device)
         tables = self._device_tables(device)
         tbl_ptrs = gpu_mod._ptr_array(
             [tables[name] for name in self._TBL_ORDER])
         scalars = (ctypes.c_long * 10)(
             len(self.templates), len(self._comment_bytes), cfg.seed,
             cfg.universe, cfg.base_date, cfg.date_step, int(permille),
-            cfg.max_comments_per_post, K, P,
+            max(1, cfg.max_comments_per_post), K, P,  # unused at rate 0
         )
         cids_t = T.tensor(np.asarray(channel_ids, dtype=np.int64),
                           device=device)
@@ -525,6 +545,7 @@ class SyntheticFeed:
         P = posts_per_channel or cfg.posts_per_channel
         K = len(channel_ids)
         N = K * P
+        self._check_comment_cfg()
         seed = np.uint64(cfg.seed)
 
         cid = np.repeat(channel_ids.astype(np.int64), P)
@@ -653,7 +674,7 @@ class SyntheticFeed:
         )
         ccnt = np.where(
             has_c, (h3 >> np.uint64(32)) % np.uint64(
-                self.cfg.max_comments_per_post
+                max(1, self.cfg.max_comments_per_post)  # unused at rate 0
             ) + np.uint64(1), 0
         ).astype(np.int32)
         meta["reply_count"] = ccnt

@@ -16,14 +16,28 @@ namespace crawl {
 
 #define HTML_BODY_CAP (64 * 1024)  // channelvalidator.go:103
 
-// Case-SENSITIVE wave-parallel substring find (patterns are <=20 bytes).
+// Wave-parallel substring find (patterns are <=20 bytes). With ``ci`` the
+// text is ASCII-case-folded, as a bytes regex under re.I folds it, and
+// the pattern must be lower case. A QUOTE_ANY pattern byte matches either
+// quote character.
+#define QUOTE_ANY '\1'
+
+DEV unsigned char ascii_lower(unsigned char c) {
+  return (c >= 'A' && c <= 'Z') ? (unsigned char)(c | 0x20) : c;
+}
+
 DEV int find_sub(const unsigned char* s, int lo, int hi, const char* pat,
-                 int plen, int lane) {
+                 int plen, int lane, bool ci = false) {
   for (int base = lo; base + plen <= hi; base += WAVE) {
     int p = base + lane;
     bool m = (p + plen <= hi);
     if (m) {
-      for (int j = 0; j < plen; ++j) m &= (s[p + j] == (unsigned char)pat[j]);
+      for (int j = 0; j < plen; ++j) {
+        unsigned char c = s[p + j];
+        if (ci) c = ascii_lower(c);
+        m &= (pat[j] == QUOTE_ANY) ? (c == '"' || c == '\'')
+                                   : (c == (unsigned char)pat[j]);
+      }
     }
     unsigned long long bal = __ballot(m);
     if (bal) return base + __ffsll(bal) - 1;
@@ -31,8 +45,9 @@ DEV int find_sub(const unsigned char* s, int lo, int hi, const char* pat,
   return -1;
 }
 
+// bytes.strip(): space \t \n \v \f \r
 DEV bool is_space(unsigned char c) {
-  return c == ' ' || c == '\t' || c == '\n' || c == '\r';
+  return c == ' ' || (c >= '\t' && c <= '\r');
 }
 
 DEV bool starts_with(const unsigned char* s, int lo, int hi,
@@ -55,11 +70,13 @@ html_classify_kernel(const unsigned char* pool, const long* doc_off,
 
     // ---- locate the <title> tag content ----
     int tlo = 0, thi = 0;
-    int tag = find_sub(s, 0, len, "<title", 6, lane);
+    // _TITLE_RE: the first <title (any case), the first '>' after it,
+    // the first </title> (any case, '>' included) after that
+    int tag = find_sub(s, 0, len, "<title", 6, lane, true);
     if (tag >= 0) {
-      int gt = find_sub(s, tag, len, ">", 1, lane);
+      int gt = find_sub(s, tag + 6, len, ">", 1, lane);
       if (gt >= 0) {
-        int close = find_sub(s, gt + 1, len, "</title", 7, lane);
+        int close = find_sub(s, gt + 1, len, "</title>", 8, lane, true);
         if (close >= 0) {
           tlo = gt + 1;
           thi = close;
@@ -79,22 +96,21 @@ html_classify_kernel(const unsigned char* pool, const long* doc_off,
     if (view_at) {
       st = 0; rs = 0;
     } else if (contact_at) {
-      // scan <meta ...> tags for name="robots" (or ') + noindex in-tag
+      // _NOINDEX_RE, all of it in any case: per <meta at m the tag runs
+      // to the first '>' (or the body end); [^>]+ puts the earliest
+      // name=<quote>robots<quote> (each quote " or ') at m+6 or later,
+      // and noindex at least one byte behind it, inside the tag
       bool noindex = false;
       int from = 0;
       while (!noindex) {
-        int m = find_sub(s, from, len, "<meta", 5, lane);
+        int m = find_sub(s, from, len, "<meta", 5, lane, true);
         if (m < 0) break;
-        int gt = find_sub(s, m, len, ">", 1, lane);
+        int gt = find_sub(s, m + 5, len, ">", 1, lane);
         int end = gt < 0 ? len : gt;
-        int rpos = find_sub(s, m, end, "name=\"robots\"", 13, lane);
-        if (rpos < 0) rpos = find_sub(s, m, end, "name='robots'", 13, lane);
-        if (rpos >= 0) {
-          // oracle regex requires noindex AFTER the name attribute
-          // within the same tag (htmlvalidator._NOINDEX_RE)
-          if (find_sub(s, rpos + 13, end, "noindex", 7, lane) >= 0)
-            noindex = true;
-        }
+        int rpos = find_sub(s, m + 6, end, "name=\1robots\1", 13, lane, true);
+        if (rpos >= 0 &&
+            find_sub(s, rpos + 14, end, "noindex", 7, lane, true) >= 0)
+          noindex = true;
         from = m + 5;
       }
       if (noindex) { st = 2; rs = 2; }       // not_found (noindex)

@@ -464,11 +464,23 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
     """Segmented per-channel engagement aggregation (SURVEY §2.6:
     GetTotalChannelViews etc. -> one workgroup per channel segment).
     Returns dict of device tensors: views/forwards/replies int64[K],
-    posts int32[K], totals int64[4] (views,forwards,replies,posts)."""
+    posts int32[K], totals int64[4] (views,forwards,replies,posts).
+
+    ``line_len`` (int32[n] on the batch's device, e.g. an EncodeResult's)
+    restricts ``posts`` to the rows with ``line_len > 0``. The kernel adds
+    into ``totals``, so the driver hands it zeros. A batch without
+    channels gives empty outputs and no launch."""
     dev = batch.device
     K = batch.n_channels
-    P = batch.n // K
+    P = batch.n // K if K else 0
     assert K * P == batch.n, "batch must be K x P channel-grouped"
+    if line_len is not None:
+        if (line_len.dtype != torch.int32 or line_len.numel() != batch.n
+                or line_len.device != dev):
+            raise ValueError(
+                f"line_len must be int32[{batch.n}] on {dev}, got "
+                f"{line_len.dtype}[{line_len.numel()}] on {line_len.device}")
+        line_len = line_len.contiguous()
     out = {
         "views": torch.zeros(K, dtype=torch.int64, device=dev),
         "forwards": torch.zeros(K, dtype=torch.int64, device=dev),
@@ -476,6 +488,8 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
         "posts": torch.zeros(K, dtype=torch.int32, device=dev),
         "totals": torch.zeros(4, dtype=torch.int64, device=dev),
     }
+    if K == 0:
+        return out
     m = batch.meta
     _call("crawl_channel_stats", m["views"], m["forwards"], m["reply_count"],
           line_len, P, K, out["views"], out["forwards"], out["replies"],
@@ -485,18 +499,29 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
 
 def reservoir_sample(batch: B.MessageBatch, k: int, seed: int = 0):
     """Per-channel uniform sample without replacement (SURVEY §2.6
-    Fisher-Yates row). Returns int32[K, k] global row indices (device)."""
+    Fisher-Yates row). Returns int32[K, min(k, P)] global row indices
+    (device): a channel with no more than ``k`` rows keeps all of them,
+    as the reference does (telegramutils.go:124)."""
     dev = batch.device
     K = batch.n_channels
-    P = batch.n // K
+    P = batch.n // K if K else 0
+    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    if k < 0:
+        raise ValueError("the sample size must not be negative")
+    k = min(k, P)
     out = torch.zeros((K, k), dtype=torch.int32, device=dev)
+    if K == 0 or k == 0:
+        return out
     _call("crawl_reservoir_sample", seed, P, K, k, out,
           min(max(1, (K + 3) // 4), 8192))
     return out
 
 
 def reservoir_sample_oracle(P: int, K: int, k: int, seed: int = 0):
-    """Python replay of the device reservoir (same splitmix stream)."""
+    """Python replay of the device reservoir (same splitmix stream);
+    like the driver, it keeps min(k, P) rows per channel."""
+    k = min(k, P)
+
     def sm64(x):
         z = (x + 0x9E3779B97F4A7C15) & (2**64 - 1)
         z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & (2**64 - 1)

@@ -677,3 +677,391 @@ def encode_yt_lines(batch):
     from crawler_amd.youtube.batch import encode_yt_batch
 
     return encode_yt_batch(batch, now=NOW)
+
+
+# ------------------------------------------------- shared GPU-test helpers
+
+def assert_batches_equal(cpu_b, dev_b):
+    """Every field of two MessageBatch objects: same dtype, shape, bits."""
+    import dataclasses
+
+    import torch
+
+    def same(name, a, b):
+        b = b.cpu()
+        assert a.dtype == b.dtype, f"{name}: {a.dtype} vs {b.dtype}"
+        assert a.shape == b.shape, f"{name}: {a.shape} vs {b.shape}"
+        assert torch.equal(a, b), (
+            f"{name} differs at "
+            f"{(a != b).nonzero()[:5].flatten().tolist()}"
+        )
+
+    for f in dataclasses.fields(cpu_b):
+        a = getattr(cpu_b, f.name)
+        b = getattr(dev_b, f.name)
+        if isinstance(a, dict):
+            assert sorted(a) == sorted(b), f"{f.name} keys differ"
+            for k in a:
+                same(f"{f.name}[{k}]", a[k], b[k])
+        elif isinstance(a, torch.Tensor):
+            same(f.name, a, b)
+        else:
+            assert a == b, f"{f.name}: {a} != {b}"
+
+
+def force_grid_one(monkeypatch, names):
+    """Patch ``gpu._call`` so that the entry points in ``names`` launch
+    one block: the grid is their last positional argument. Returns the
+    list the patched calls are recorded in."""
+    from crawler_amd.ops import gpu
+
+    real, seen = gpu._call, []
+
+    def call(name, *args, **kw):
+        if name in names:
+            assert isinstance(args[-1], int) and args[-1] >= 1, name
+            args = args[:-1] + (1,)
+            seen.append(name)
+        return real(name, *args, **kw)
+
+    monkeypatch.setattr(gpu, "_call", call)
+    return seen
+
+
+def forbid_launches(monkeypatch):
+    """Patch ``gpu._call`` to fail: the code under test must not launch."""
+    from crawler_amd.ops import gpu
+
+    def call(name, *args, **kw):
+        raise AssertionError(f"unexpected launch of {name}")
+
+    monkeypatch.setattr(gpu, "_call", call)
+
+
+# ----------------------------------------------------- feed generator matrix
+
+FEED_SHAPES = [(1, 1), (1, 3), (2, 1), (3, 5), (5, 257), (1, 1025)]
+FEED_BIG = (5, 7000)          # 35 000 messages > 8192 blocks x 4 waves
+FEED_FORCED = [(3, 5), (5, 257)]
+# the forced-grid runs: one block of 256 threads has to stride over the
+# comments too, so every second message carries up to three
+FEED_FORCED_CFG = dict(seed=79, universe=100_000, comment_rate=0.5,
+                       max_comments_per_post=3)
+
+
+def feed_cases():
+    """[(name, FeedConfig keywords, channel ids, posts per channel)]: the
+    matrix both builders run over."""
+    base = dict(seed=77, universe=100_000)
+    cases = []
+    for K, P in FEED_SHAPES + [FEED_BIG]:
+        cases.append(("shape-%dx%d" % (K, P), base, list(range(10, 10 + K)),
+                      P))
+    cases.append(("ids-unsorted", base, [905, 3, 77_000, 12, 4], 33))
+    cases.append(("ids-duplicate", base, [7, 7, 3], 33))
+    cases.append(("ids-extremes", dict(seed=77, universe=1000),
+                  [0, 999, 1000, 2 ** 40], 33))
+    for rate in (0.0, 0.001, 0.5, 1.0):
+        for mc in (1, 3, 50):
+            cases.append(("rate-%s-max-%d" % (rate, mc),
+                          dict(base, comment_rate=rate,
+                               max_comments_per_post=mc), [5, 6, 9], 40))
+    cases.append(("rate-1.0-one-post",
+                  dict(base, comment_rate=1.0), [5, 6, 9], 1))
+    for universe in (1, 2, 10 ** 10 - 1):
+        cases.append(("universe-%d" % universe,
+                      dict(seed=77, universe=universe), [1, 8], 50))
+    for seed in (0, 1, 2 ** 63 - 1, 2 ** 63, 2 ** 64 - 1):
+        cases.append(("seed-%d" % seed, dict(seed=seed, universe=100_000),
+                      [1, 8], 50))
+    # dates 2**31 - 100 + 7 * p (+ 0..29): the first posts stay below
+    # 2**31, the later ones wrap through int32
+    cases.append(("dates-wrap", dict(base, base_date=2 ** 31 - 100,
+                                     date_step=7), [1, 8], 50))
+    return cases
+
+
+def feed_entity_templates():
+    """A template set whose messages carry 0, 1, 4 and 70 entity rows
+    (the standard set stops at one): rows with and without a url inside
+    one message, and more rows than a wave has lanes."""
+    from crawler_amd.feed.synth import Template
+
+    return [
+        Template(name="none", content_type="messageText",
+                 text="без ссылок 🚀"),
+        Template(name="one", content_type="messageText",
+                 text="спасибо @{U} за наводку",
+                 entity_specs=[("mention", 0)]),
+        Template(name="four", content_type="messageText", weight=2.0,
+                 text=("спасибо @{U} 🙏 источник: https://t.me/{U} — "
+                       "click here и ещё @{U}"),
+                 entity_specs=[("mention", 0), ("url", 1), ("text_url", 0),
+                               ("mention", 2)]),
+        Template(name="seventy", content_type="messagePhoto",
+                 text="@{U} " * 70, has_thumb=True,
+                 entity_specs=[("mention", j) for j in range(70)]),
+    ]
+
+
+FEED_ENTITY_CASE = (dict(seed=80, universe=100_000, comment_rate=0.5),
+                    [3, 1, 4], 21)
+
+
+# ------------------------------------------------------- t.me HTML corpora
+
+HTML_VALID = ("valid", "")
+HTML_NOT_CHANNEL = ("not_channel", "not_supergroup")
+HTML_NOT_FOUND = ("invalid", "not_found")
+HTML_UNRECOGNIZED = ("invalid", "unrecognized")
+
+_CONTACT = b"<title>Telegram: Contact @a</title>"
+_ROBOTS = b'<meta name="robots" content="noindex">'
+
+# documents on which the kernel was read to disagree with the oracle, with
+# the oracle's answer
+HTML_TABLE_ROWS = [
+    (b"<TITLE>Telegram: View @a</TITLE>", HTML_VALID),
+    (b"<title>\x0cView @a</title>", HTML_VALID),
+    (b"<title>Foo</title x>Telegram: View @a</title>", HTML_VALID),
+    (_CONTACT + b'<META NAME="ROBOTS" CONTENT="NOINDEX">', HTML_NOT_FOUND),
+    (_CONTACT + b'<meta name="robots\' content=\'noindex\'>',
+     HTML_NOT_FOUND),
+    (_CONTACT + b'<meta name=\'robots\' content="noindex" name="robots">',
+     HTML_NOT_FOUND),
+    (_CONTACT + b'<metaname="robots" content="noindex">', HTML_NOT_CHANNEL),
+    (_CONTACT + b'<meta name="robots"noindex>', HTML_NOT_CHANNEL),
+]
+
+HTML_RULES = [b"View @", b"Telegram: View @", b"Contact @",
+              b"Telegram: Contact @", b"Telegram Messenger"]
+
+
+def html_rule_docs():
+    """Each title rule at the start, in the middle and at the end of the
+    title, bare and behind every strippable byte; the title tag's forms;
+    the noindex forms."""
+    docs = []
+    for rule in HTML_RULES:
+        for title in (rule + b"a tail", b"head " + rule + b"a tail",
+                      b"head " + rule, rule,
+                      b" \t\n\r\x0b\x0c" + rule + b"a \x0c\x0b\r\n\t ",
+                      b"\x0b" + rule + b"a", b"\xa0" + rule + b"a",
+                      b"\x1c" + rule + b"a", rule[:-1], rule.lower(),
+                      rule.upper()):
+            docs.append(b"<html><title>" + title + b"</title>" + _ROBOTS)
+            docs.append(b"<title>" + title + b"</title>")
+    v = b"View @a"
+    docs += [
+        b"<title lang=en>" + v + b"</title>",
+        b"<titlex>" + v + b"</title>",
+        b"<TiTlE LANG='en'>" + v + b"</tItLe>",
+        b"<title " + v,                              # no '>' at all
+        b"<title " + v + b"</title>",                # its only '>' closes
+        b"<title " + v + b"</title></title>",
+        b"<title>" + v,                              # no close tag
+        b"<title>" + v + b"</title",
+        b"<title>" + v + b"< /title>",
+        b"<title></title>",
+        b"<title> \t\n\r\x0b\x0c</title>",
+        b"<title>" + v + b"</title><title>Telegram Messenger</title>",
+        b"<title>Telegram Messenger</title><title>" + v + b"</title>",
+        b"<title>x</title><title>" + v + b"</title>",
+        b"<title><title>" + v + b"</title>",
+        b"<titl>" + v + b"</title>",
+        b"< title>" + v + b"</title>",
+        b"</title><title>" + v + b"</title>",
+        b"<title>Telegram Messenger</title>" + _ROBOTS,
+        b"<html><head></head><body>no title</body></html>",
+        b"<", b">", b"<title", b"<title>", b"</title>", b"\x00",
+    ]
+    c = _CONTACT
+    docs += [
+        c,
+        c + _ROBOTS,
+        _ROBOTS + c,                                  # meta before the title
+        c + b'<meta content="noindex" name="robots">',   # only before name=
+        c + b'<meta name="robots"><meta content="noindex">',  # later tag
+        c + b'<meta name="robots" content="index">noindex',   # body text
+        c + b'<meta name="robots" content="index"> noindex <p>',
+        c + b'<meta name="robots" content="noindex"',    # unterminated
+        c + b'<meta name="robots" content="noinde',
+        c + b'<meta name="robots" content="noindex',
+        c + b"<meta",
+        c + b"<meta ",
+        c + b'<meta name="robots"',
+        c + b'<meta name="robots" ',
+        c + (b'<meta name="description" content="noindex">'
+             b'<meta name="robots" content="all">'
+             b'<meta name="viewport">' + _ROBOTS),    # only the last matches
+        c + (b'<meta name="robots" content="all">') * 3,
+        c + b"<meta" + _ROBOTS,                       # <meta<meta ...
+        c + b"<meta><meta><meta" + _ROBOTS,
+        c + b'<meta x name="robots" y noindex>',
+        c + b'<meta name="robots" noindex>',
+        c + b'<meta name="robots"_noindex>',
+        c + b'<meta name="robots" NoInDeX>',
+        c + b"<mEtA nAmE='rObOtS\" content=noindex>",
+        c + b'<meta name=robots content="noindex">',   # no quotes
+        c + b'<meta name="robots content="noindex">',
+        c + b'<meta name= "robots" content="noindex">',
+        c + b'<meta name="robot" name="robots" content="noindex">',
+        c + b'<meta name="robots" content="no index">',
+        c + b'<meta\nname="robots"\ncontent="noindex"\n>',
+        c + b'<link name="robots" content="noindex">',
+        c + b'<meta name="robots"> <meta noindex>',
+        c + b'<meta name="robots" content=">" noindex>',
+        b"<title>Contact @a</title>" + _ROBOTS,
+        b"<title>Contact @a</title>",
+    ]
+    return docs
+
+
+HTML_EDGE_OFFSETS = list(range(58, 71)) + list(range(122, 135))
+
+
+def html_window_edges():
+    """[(kind, offset, doc, oracle answer)]: each pattern the kernel
+    searches for, starting ``offset`` bytes into the range it is searched
+    in (a 64-lane window walks that range). A missed pattern changes the
+    answer: valid becomes unrecognized, not_found becomes not_channel."""
+    v = b"View @a"
+    out = []
+    for off in HTML_EDGE_OFFSETS:
+        pad = b"x" * off
+        out += [
+            # range: the whole body
+            ("title_open", off, pad + b"<title>" + v + b"</title>",
+             HTML_VALID),
+            # range: from behind '<title'
+            ("title_gt", off, b"<title" + b" " * off + b">" + v
+             + b"</title>", HTML_VALID),
+            # range: from behind the tag's '>'
+            ("title_close", off, b"<title>" + v + b"x" * (off - len(v))
+             + b"</title>", HTML_VALID),
+            # range: the whole body (the first <meta)
+            ("meta_first", off, b"<title>Contact @a</title>"
+             + b"x" * (off - 25) + _ROBOTS, HTML_NOT_FOUND),
+            # range: from behind the previous '<meta'
+            ("meta_next", off, b"<meta>" + pad[1:] + _ROBOTS + _CONTACT,
+             HTML_NOT_FOUND),
+            # range: from m + 6
+            ("name", off, _CONTACT + b"<meta " + b"a" * off
+             + b'name="robots" content="noindex">', HTML_NOT_FOUND),
+            # range: from r + 14
+            ("noindex", off, _CONTACT + b'<meta name="robots"_'
+             + b"a" * off + b"noindex>", HTML_NOT_FOUND),
+        ]
+    return out
+
+
+def html_short_ranges():
+    """Search ranges shorter than the pattern searched in them."""
+    c = _CONTACT
+    return [
+        b"", b"<", b"<titl", b"<title", b"<title>",
+        b"<title>V</title>", b"<title>View </title>",
+        b"<title>View @</title>", b"<title>Contact </title>",
+        b"<title>Telegram Messenge</title>",
+        b"<title>View @a</titl", b"<title>View @a</title",
+        b"<title>View @a<", b"<title>View @a",
+        c + b"<", c + b"<met", c + b"<meta", c + b"<meta n",
+        c + b"<meta name=", c + b'<meta name="robots',
+        c + b'<meta name="robots"', c + b'<meta name="robots" ',
+        c + b'<meta name="robots" n', c + b'<meta name="robots" noinde',
+        c + b'<meta name="robots" noindex',
+        c + b'<meta name="robots">noindex',
+    ]
+
+
+HTML_CAP = 64 * 1024
+
+
+def html_cap_docs():
+    """[(doc, oracle answer)] around the 64 KiB body cap."""
+    def titled(total):
+        # '</title>' ends at byte ``total``
+        body = b"<title>View @a"
+        return body + b"x" * (total - len(body) - 8) + b"</title>"
+
+    def meta_ending_at(end, tail):
+        head = _CONTACT
+        meta = b'<meta name="robots" content="noindex'
+        return head + b"x" * (end - len(head) - len(meta)) + meta + tail
+
+    behind = _CONTACT + b"x" * (HTML_CAP - len(_CONTACT)) + _ROBOTS
+    behind += b"y" * (70_000 - len(behind))
+    return [
+        (titled(HTML_CAP), HTML_VALID),
+        (titled(HTML_CAP + 1), HTML_UNRECOGNIZED),
+        (titled(HTML_CAP + 1) + b"<title>View @b</title>",
+         HTML_UNRECOGNIZED),
+        (behind, HTML_NOT_CHANNEL),
+        # 'noindex' ends at the cap, with the tag's '>' behind it
+        (meta_ending_at(HTML_CAP, b'">'), HTML_NOT_FOUND),
+        # ... and one byte later, so the cap cuts its 'x'
+        (meta_ending_at(HTML_CAP + 1, b'">'), HTML_NOT_CHANNEL),
+    ]
+
+
+def html_packing_docs():
+    """Documents to classify back to back, in this order: document 2j ends
+    1..8 bytes short of completing '</title>' (or 'noindex'), and document
+    2j+1 starts with the missing bytes. Reading past a document's end
+    turns unrecognized into valid, and not_channel into not_found."""
+    docs = []
+    full = b"<title>View @a</title>"
+    for cut in range(1, 9):
+        docs.append(full[:-cut])
+        docs.append(full[-cut:] + b"<title>Telegram Messenger</title>")
+    full = _CONTACT + b'<meta name="robots" content="noindex'
+    for cut in range(1, 8):
+        docs.append(full[:-cut])
+        docs.append(full[-cut:] + b'"><title>View @b</title>')
+    return docs
+
+
+_HTML_TOKENS = [
+    b"<title", b"<TITLE", b">", b"</title>", b"</TITLE>", b"</title",
+    b"View @", b"Telegram: View @", b"Contact @", b"Telegram: Contact @",
+    b"Telegram Messenger", b"<meta", b"<META", b" ", b"\x0c", b"\n",
+    b'name="robots"', b"name='robots'", b'NAME="Robots\'', b"name=",
+    b"robots", b'"', b"'", b"noindex", b"NOINDEX", b"noinde", b"x", b"a",
+    b"<", b"=", b"content=", b"x" * 61,
+]
+
+
+def html_fuzz_docs(seed, n):
+    """Token soup over the pieces the two regexes look for."""
+    rng = random.Random(seed)
+    docs = []
+    for _ in range(n):
+        head = rng.choice([b"", b"<title>Telegram: Contact @a</title>",
+                           b"<title>Contact @a</title>"])
+        docs.append(head + b"".join(
+            rng.choice(_HTML_TOKENS) for _ in range(rng.randrange(0, 30))))
+    return docs
+
+
+def html_corpus():
+    """{group: [doc, ...]}: every hand-made t.me document, and one
+    fixed-seed fuzz."""
+    return {
+        "fuzz": html_fuzz_docs(20260304, 1500),
+        "table": [d for d, _ in HTML_TABLE_ROWS],
+        "rules": html_rule_docs(),
+        "edges": [d for _, _, d, _ in html_window_edges()],
+        "short": html_short_ranges(),
+        "cap": [d for d, _ in html_cap_docs()],
+        "packing": html_packing_docs(),
+    }
+
+
+def html_oracle(docs):
+    from crawler_amd.engine.htmlvalidator import parse_channel_html
+
+    out = []
+    for d in docs:
+        r = parse_channel_html(d)
+        out.append((r.status, r.reason))
+    return out

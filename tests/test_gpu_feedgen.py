@@ -1,36 +1,13 @@
 """Device feed generator (csrc/feedgen.hip) vs the numpy oracle:
 every tensor of the packed batch must be bit-identical."""
-import dataclasses
-
 import numpy as np
 import pytest
 import torch
 
+from _corpora import assert_batches_equal as _assert_batches_equal
 from crawler_amd.feed import FeedConfig, SyntheticFeed
 
 pytestmark = pytest.mark.gpu
-
-
-def _assert_batches_equal(cpu_b, dev_b):
-    for f in dataclasses.fields(cpu_b):
-        a = getattr(cpu_b, f.name)
-        b = getattr(dev_b, f.name)
-        if isinstance(a, dict):
-            for k in a:
-                bb = b[k].cpu()
-                assert torch.equal(a[k], bb), (
-                    f"meta[{k}] differs: "
-                    f"{(a[k] != bb).nonzero()[:5].flatten().tolist()}"
-                )
-        elif isinstance(a, torch.Tensor):
-            bb = b.cpu()
-            assert a.shape == bb.shape, f"{f.name}: {a.shape} vs {bb.shape}"
-            assert torch.equal(a, bb), (
-                f"{f.name} differs at "
-                f"{(a != bb).nonzero()[:5].flatten().tolist()}"
-            )
-        else:
-            assert a == b, f"{f.name}: {a} != {b}"
 
 
 def test_device_generation_bit_identical():
