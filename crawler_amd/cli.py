@@ -101,6 +101,8 @@ def build_parser() -> argparse.ArgumentParser:
       help="youtube random sampling: upper bound on prefix searches")
     a("--yt-daily-quota", type=int, default=10_000,
       help="youtube: API quota units available to the crawl")
+    a("--sample-seed", type=int, default=0,
+      help="with --gpu, the seed of the --sample-size sample")
     a("--yt-gpu-snowball", action="store_true",
       help="youtube: with --gpu, run snowball sampling on the GPU too")
     return p
@@ -169,6 +171,7 @@ def parse_config(argv: Optional[List[str]] = None) -> CrawlerConfig:
         disable_rate_limits=args.disable_rate_limits,
         yt_max_searches=args.yt_max_searches,
         yt_daily_quota=args.yt_daily_quota,
+        sample_seed=args.sample_seed,
     )
     if args.min_post_date:
         import datetime as dt

@@ -99,6 +99,7 @@ class CrawlerConfig:
     disable_rate_limits: bool = False   # neutralize pacing for benchmarks
     yt_max_searches: int = 200          # GetRandomVideos search bound
     yt_daily_quota: int = 10_000        # YouTube API units per day
+    sample_seed: int = 0                # --gpu: seed of the --sample-size keys
 
     # Runtime-injected (not a flag)
     null_validator: object = None

@@ -15,6 +15,22 @@ Equivalence contract: for the same channels the JSONL bytes are identical
 to the CPU pipeline's Post.to_jsonl() output (enforced by the byte-exact
 kernel tests) and the discovered-channel set matches golden extraction.
 
+Fetch window: with --date-between, --max-posts or --sample-size set
+(ops.gpu.window_params), a chunk first goes through the fetch-window
+kernel (csrc/fetch_window.hip), the row form of fetch_channel_messages'
+walk, and only the kept rows (batch.select_rows) are encoded, claimed and
+written; a channel then owns kept[k] lines, not P, and one with no kept
+row writes and truncates nothing. Without sampling the kept set is the
+CPU path's. With --sample-size the two paths agree in the sample's size,
+in drawing a uniform subset of the same window and in being
+deterministic, but not in WHICH posts are drawn or in their order: the
+CPU path shuffles with Python's random (Fisher-Yates) and writes the
+sample in shuffled order; this path keeps the sample_size smallest
+splitmix64 keys of (--sample-seed, chat_id, msg_id) and writes them in
+row order, so the sample does not depend on chunk_channels. With none of
+the three flags set the window kernel is never launched and min_post_date
+stays a per-row filter inside parse+encode.
+
 Cross-rank: ranks shard the layer's channels; newly-claimed hashes are
 all-gathered and merged into each rank's SeenSet (bench.py does the same
 per step) so a channel is crawled by exactly one rank per crawl.
@@ -92,6 +108,9 @@ class GpuCrawlEngine:
         self.last_deadends = set(bad)
         for u in bad:
             self.stats["deadends"] += 1
+        # None = no fetch window: the per-row min_post_date filter of
+        # parse+encode does everything
+        window = self.gpu.window_params(self.cfg)
         for ci, i in enumerate(range(0, len(ok), self.chunk_channels)):
             chunk = ok[i:i + self.chunk_channels]
             cids = np.array([c for _u, c in chunk], dtype=np.int64)
@@ -99,6 +118,20 @@ class GpuCrawlEngine:
             batch = self.feed.build_batch_device(
                 cids, self.device, posts_per_channel=self.ppc
             )
+            kept_k = None
+            if window is not None:
+                # fetch window (date-between / max-posts / sample-size):
+                # only the kept rows are encoded, claimed and written
+                keep, kept = self.gpu.fetch_window(batch, **window)
+                kept_k = kept.cpu().numpy().astype(np.int64)
+                if not kept_k.any():
+                    # nothing of this chunk is inside the window: no
+                    # lines, no links, and no deadends either (below)
+                    self.stats["pages"] += len(chunk)
+                    t["gen+kernels"] += _time.perf_counter() - t0
+                    continue
+                from ..ops import batch as _B
+                batch = _B.select_rows(batch, keep.nonzero().flatten())
             res = self.gpu.parse_encode(
                 batch, now=now, min_post_date=self.cfg.min_post_date
             )
@@ -134,11 +167,24 @@ class GpuCrawlEngine:
             K = len(chunk)
             # vectorized per-channel ranges/counts (a python loop over
             # numpy scalars costs ~0.3s per 1500 channels)
-            off2 = line_off.reshape(K, P)
-            len2 = line_len.reshape(K, P)
-            lo_k = off2[:, 0]
-            hi_k = off2[:, -1] + len2[:, -1]
-            n_lines_k = (len2 > 0).sum(axis=1)
+            if kept_k is None:
+                off2 = line_off.reshape(K, P)
+                len2 = line_len.reshape(K, P)
+                lo_k = off2[:, 0]
+                hi_k = off2[:, -1] + len2[:, -1]
+                n_lines_k = (len2 > 0).sum(axis=1)
+            else:
+                # windowed: channel k owns the kept[k] lines from the
+                # exclusive cumsum of kept on; none = an empty range
+                end_k = np.cumsum(kept_k)
+                beg_k = end_k - kept_k
+                some = kept_k > 0
+                last = np.maximum(end_k - 1, 0)
+                lo_k = np.where(some, line_off[np.minimum(beg_k, last)], 0)
+                hi_k = np.where(some, line_off[last] + line_len[last], 0)
+                written = np.concatenate(
+                    ([0], np.cumsum(line_len > 0, dtype=np.int64)))
+                n_lines_k = written[end_k] - written[beg_k]
             posts_total += int(n_lines_k.sum())
             self.stats["pages"] += K
             items = []

@@ -77,6 +77,9 @@ _SIGNATURES = {
     "crawl_reservoir_sample": [_cl, _ci, _ci, _ci, _vp_t, _ci, _vp_t],
     "crawl_html_classify": [_vp_t, _vp_t, _vp_t, _ci, _vp_t, _vp_t, _ci,
                             _vp_t],
+    # fetch_window.hip
+    "crawl_fetch_window": [_vp_t, _vp_t, _vp_t, _ci, _ci] + [_cl] * 5
+                          + [_vp_t, _vp_t, _ci, _vp_t],
     # yt_encode.hip
     "crawl_yt_ptr_count": [],
     "crawl_yt_measure": [_pp, _lp, _vp_t, _ci, _vp_t],
@@ -539,6 +542,108 @@ def reservoir_sample_oracle(P: int, K: int, k: int, seed: int = 0):
                 slot[j] = c * P + i
         out.append(slot)
     return out
+
+
+class FetchWindowResult(tuple):
+    """``(keep, kept)`` of fetch_window. ``raw_keep`` / ``raw_kept`` are
+    the guarded allocations they are views into (test seam ``_guard`` >
+    0), else None."""
+
+    raw_keep: Optional[torch.Tensor] = None
+    raw_kept: Optional[torch.Tensor] = None
+
+    def __new__(cls, keep, kept, raw_keep=None, raw_kept=None):
+        self = super().__new__(cls, (keep, kept))
+        self.raw_keep = raw_keep
+        self.raw_kept = raw_kept
+        return self
+
+
+def fetch_window(batch: B.MessageBatch, stop_below: Optional[int] = None,
+                 skip_above: Optional[int] = None, cap: int = 0,
+                 sample_k: int = 0, seed: int = 0, *,
+                 _poison: Optional[int] = None, _guard: int = 0):
+    """Which rows of a K x P channel-grouped batch the crawl keeps
+    (FetchChannelMessagesWithSampling, telegramutils.go:25-157; oracle:
+    golden_window.fetch_window). Per channel, newest row first: a row
+    dated after ``skip_above`` is skipped, the first other row dated
+    before ``stop_below`` ends the walk, and so does the ``cap``-th
+    candidate (0 = no cap); of more than ``sample_k`` candidates (0 = no
+    sampling) the ``sample_k`` with the smallest
+    ``golden_window.sample_key`` stay. Bounds are unix seconds, None =
+    unbounded; ``seed`` is taken modulo 2**64.
+
+    Returns ``(keep uint8[n], kept int32[K])`` on the batch's device.
+    The kernel writes every element of both. A batch without channels
+    gives empty outputs and no launch.
+
+    ``_poison`` / ``_guard`` are the test seams of :func:`parse_encode`
+    (off by default): the guarded buffers are the result's ``.raw_keep``
+    and ``.raw_kept`` (``_guard`` counts elements)."""
+    dev = batch.device
+    K = batch.n_channels
+    P = batch.n // K if K else 0
+    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    if cap < 0 or sample_k < 0:
+        raise ValueError("cap and sample_k must not be negative")
+    keep, raw_keep = _alloc_out(batch.n, dev, _poison, _guard)
+    if _poison is None and _guard <= 0:
+        kept, raw_kept = torch.empty(K, dtype=torch.int32, device=dev), None
+    else:
+        g = max(_guard, 0)
+        fill = 0xA5 if _poison is None else _poison
+        raw_kept = torch.full((4 * (K + 2 * g),), fill, dtype=torch.uint8,
+                              device=dev).view(torch.int32)
+        kept = raw_kept[g:g + K]
+    if K == 0:
+        return FetchWindowResult(keep, kept, raw_keep, raw_kept)
+    from .golden_window import NO_SKIP, NO_STOP
+
+    clamp = lambda v: max(NO_STOP, min(NO_SKIP, int(v)))
+    lo = NO_STOP if stop_below is None else clamp(stop_below)
+    hi = NO_SKIP if skip_above is None else clamp(skip_above)
+    seed = ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    date = batch.meta["date"]
+    for nm, t, dt_ in (("date", date, torch.int32),
+                       ("chat_id", batch.chat_id, torch.int64),
+                       ("msg_id", batch.msg_id, torch.int64)):
+        assert t.dtype == dt_ and t.device == dev and t.is_contiguous(), nm
+        assert t.numel() == batch.n, nm
+    _call("crawl_fetch_window", date, batch.chat_id, batch.msg_id, P, K, lo,
+          hi, int(cap), int(sample_k), seed, keep, kept,
+          min((K + 3) // 4, 8192))
+    return FetchWindowResult(keep, kept, raw_keep, raw_kept)
+
+
+def window_params(cfg) -> Optional[dict]:
+    """The :func:`fetch_window` arguments a CrawlerConfig asks for, or
+    None when the GPU crawl's per-row ``min_post_date`` filter already
+    does all of it (no date-between window, no ``max_posts`` cap, no
+    sampling). Precedence is ``engine.pipeline.fetch_channel_messages``':
+    both date-between bounds set -> that window, ``min_post_date``
+    ignored; otherwise ``min_post_date`` alone stops the walk. Sampling
+    needs ``date_between_min`` (``_maybe_sample``). The CPU compares
+    integer dates with float timestamps: ``d > hi`` is ``d > floor(hi)``
+    and ``d < lo`` is ``d < ceil(lo)``."""
+    import math
+
+    stop = skip = None
+    window = (cfg.date_between_min is not None
+              and cfg.date_between_max is not None)
+    if window:
+        stop = math.ceil(cfg.date_between_min.timestamp())
+        skip = math.floor(cfg.date_between_max.timestamp())
+    elif cfg.min_post_date is not None:
+        stop = math.ceil(cfg.min_post_date.timestamp())
+    cap = cfg.max_posts if cfg.max_posts and cfg.max_posts > 0 else 0
+    sample_k = (cfg.sample_size
+                if (cfg.sample_size and cfg.sample_size > 0
+                    and cfg.date_between_min is not None) else 0)
+    if not window and cap == 0 and sample_k == 0:
+        return None
+    return {"stop_below": stop, "skip_above": skip, "cap": int(cap),
+            "sample_k": int(sample_k),
+            "seed": int(getattr(cfg, "sample_seed", 0))}
 
 
 _HTML_STATUS = ["valid", "not_channel", "invalid"]

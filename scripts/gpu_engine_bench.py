@@ -42,6 +42,13 @@ def main():
     ap.add_argument("--walkback-rate", type=int, default=15)
     ap.add_argument("--pipelined", action="store_true",
                     help="two half-pools: device stage overlaps host tail")
+    ap.add_argument("--date-between-ts", default="",
+                    help="snowball: LO,HI unix seconds of a --date-between "
+                         "fetch window")
+    ap.add_argument("--max-posts", type=int, default=-1,
+                    help="snowball: --max-posts of the crawl")
+    ap.add_argument("--sample-size", type=int, default=0,
+                    help="snowball: --sample-size (with --date-between-ts)")
     args = ap.parse_args()
 
     if args.mode == "randomwalk":
@@ -54,7 +61,14 @@ def main():
         sampling_method="snowball", max_depth=args.max_depth, min_users=1,
         max_pages=args.max_pages,
         skip_media_download=True,
+        max_posts=args.max_posts,
     )
+    if args.date_between_ts:
+        import datetime as dt
+        lo, hi = (float(x) for x in args.date_between_ts.split(","))
+        cfg.date_between_min = dt.datetime.fromtimestamp(lo, dt.timezone.utc)
+        cfg.date_between_max = dt.datetime.fromtimestamp(hi, dt.timezone.utc)
+        cfg.sample_size = args.sample_size
     feed = SyntheticFeed(FeedConfig(seed=2026, universe=args.universe,
                                     posts_per_channel=args.posts))
     sm = LocalStateManager(cfg)
@@ -79,6 +93,9 @@ def main():
         "discovered": stats["discovered"],
         "deadends": stats["deadends"],
         "max_depth": args.max_depth,
+        "date_between_ts": args.date_between_ts or None,
+        "max_posts": args.max_posts,
+        "sample_size": args.sample_size,
     }
     if getattr(eng, "timings", None):
         out["phase_s"] = {k: round(v, 3) for k, v in eng.timings.items()}
