@@ -13,6 +13,17 @@ Outlink validation in the synthetic world: a name is a valid channel iff
 it decodes to a universe id (the SearchPublicChat equivalent — the live
 check the reference does at crawl/runner.go:1310-1383) and passes
 FilterUsername and the invalid-channel cache.
+
+Fetch and deadend flags: with --date-between, --max-posts, --sample-size,
+--min-post-date, --time-ago or --max-comments set, a hop runs the fetch
+window, the channel gate and the compact-rows kernel (ops.gpu) before
+parse+encode, as the BFS engine does (engine/gpu_runner.py): a walker then
+owns kept[k] rows, not P, and the walker of a link comes from the
+compaction's row-to-walker map. An active walker without a kept row
+writes nothing and walks back; an inactive one is a deadend: its page is
+counted and deleted, and its chain ends. With none of the flags set a hop
+launches what it always did. --min-users, --tandem-crawl and
+--max-crawl-duration are not applied here.
 """
 from __future__ import annotations
 
@@ -46,7 +57,7 @@ class GpuRandomWalk:
         self.rng = rng or random.Random()
         self.seen = gpu_mod.SeenSet(self.device)
         self.stats = {"pages": 0, "posts": 0, "invalid_400": 0,
-                      "walkback_exhausted": 0, "edges": 0}
+                      "walkback_exhausted": 0, "edges": 0, "deadends": 0}
         self._pin_ring = [None, None]       # pinned host JSONL slots
         self._spill_tickets = [None, None]  # native-sink tickets
         self._inflight_paths = {}           # slot -> channel set
@@ -251,7 +262,8 @@ class GpuRandomWalk:
 
     def _hop_gpu(self, live: List[Page], slot: int,
                  now: Optional[_dt.datetime] = None) -> dict:
-        """Device stage: feedgen -> parse/encode -> seen claim ->
+        """Device stage: feedgen -> (with a fetch or deadend flag: fetch
+        window -> channel gate -> kept rows) -> parse/encode -> seen claim ->
         device dedup + validation -> host pulls + async JSONL D2H.
         Returns the host-side payload for _hop_host. Safe to run on a
         worker thread (GPU + numpy only; no rng, no store writes — the
@@ -267,6 +279,29 @@ class GpuRandomWalk:
         torch.cuda.synchronize()
         self.timings["feedgen"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
+        fetch = self._fetch_flags()
+        kept_k = active_k = row_channel = None
+        if fetch is not None:
+            # fetch window -> activity gate -> kept rows: a walker owns
+            # kept[k] rows, not P, so the row-to-walker map travels with
+            # the rows (row_channel). The window applies min_post_date
+            # as the CPU walk does, so parse+encode gets no date filter.
+            window, gate, max_comments = fetch
+            keep, kept = self.gpu.fetch_window(batch, **window)
+            if gate is not None:
+                keep, kept, active, _latest = self.gpu.channel_gate(
+                    batch, keep, kept, **gate)
+                active_k = active.cpu().numpy() != 0
+            rows, row_channel = self.gpu.compact_rows(batch, keep, kept)
+            kept_k = kept.cpu().numpy().astype(np.int64)
+            if rows.numel() == 0:
+                # no walker kept a row: nothing to encode, claim or
+                # copy; the host tails still run (walk back / deadend)
+                self.timings["kernels"] += _time.perf_counter() - t0
+                return self._empty_payload(slot, now, kept_k, active_k)
+            from ..ops import batch as _B
+            batch = self.gpu.cap_comments(_B.select_rows(batch, rows),
+                                          max_comments)
         res = self.gpu.parse_encode(batch, now=now)
         self.seen.claim(res)
         torch.cuda.synchronize()
@@ -289,7 +324,10 @@ class GpuRandomWalk:
                   < cnt_g[:, None])
         nz = mask_g.nonzero()
         mi_g, si_g = nz[:, 0], nz[:, 1]
-        wk_g = torch.div(mi_g, P, rounding_mode="floor")
+        if row_channel is None:
+            wk_g = torch.div(mi_g, P, rounding_mode="floor")
+        else:
+            wk_g = row_channel[mi_g].to(torch.int64)
         # zero-padded rows for ALL pairs, then a byte-LEXICOGRAPHIC sort
         # within each walker (names pack into 4 big-endian int64 keys:
         # lexicographic byte order == big-endian integer order). Exact
@@ -354,7 +392,41 @@ class GpuRandomWalk:
                 "res_out": res.out, "line_off": line_off,
                 "line_len": line_len, "u_w": u_w, "u_h": u_h,
                 "u_rows": u_rows, "ok_all": ok_all,
-                "cid_ok_all": cid_ok_all, "w": w, "now": now}
+                "cid_ok_all": cid_ok_all, "w": w, "now": now,
+                "kept_k": kept_k, "active_k": active_k}
+
+    def _fetch_flags(self):
+        """None when no fetch or deadend flag is set (the hop then
+        launches what it always did), else ``(window, gate,
+        max_comments)``: the fetch_window arguments (forced: the walk
+        needs keep/kept whatever the flag), the channel_gate arguments
+        or None, and the comment cap (negative = none)."""
+        cfg = self.cfg
+        max_comments = getattr(cfg, "max_comments", -1)
+        if max_comments is None:
+            max_comments = -1
+        gate = self.gpu.gate_params(cfg)
+        if (self.gpu.window_params(cfg) is None and gate is None
+                and cfg.min_post_date is None and max_comments < 0):
+            return None
+        return (self.gpu.window_params(cfg, force=True), gate,
+                max_comments)
+
+    @staticmethod
+    def _empty_payload(slot: int, now, kept_k, active_k) -> dict:
+        """The payload of a hop in which no walker kept a row."""
+        w = 32
+        return {"slot": slot,
+                "out_host": torch.empty(0, dtype=torch.uint8), "ev": None,
+                "res_out": None,
+                "line_off": np.zeros(0, dtype=np.int64),
+                "line_len": np.zeros(0, dtype=np.int32),
+                "u_w": np.zeros(0, dtype=np.int32),
+                "u_h": np.zeros(0, dtype=np.int64),
+                "u_rows": np.zeros((0, w), dtype=np.uint8),
+                "ok_all": np.zeros(0, dtype=bool),
+                "cid_ok_all": np.zeros(0, dtype=bool), "w": w, "now": now,
+                "kept_k": kept_k, "active_k": active_k}
 
     def _hop_host(self, live: List[Page], payload: dict) -> None:
         """Host tail: spill, validation cache, admission, walk
@@ -372,18 +444,35 @@ class GpuRandomWalk:
         cid_ok_all = payload["cid_ok_all"]
         w = payload["w"]
         P = self.ppc
-        payload["ev"].synchronize()   # JSONL bytes landed in the ring
+        kept_k = payload.get("kept_k")
+        active_k = payload.get("active_k")
+        if payload["ev"] is not None:
+            payload["ev"].synchronize()   # JSONL bytes landed in the ring
         payload["res_out"] = None
         self.timings["d2h"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
 
         # spill JSONL per channel (K x P layout) in ONE native-sink call
         K = len(live)
-        off2 = line_off.reshape(K, P)
-        len2 = line_len.reshape(K, P)
-        lo_k = off2[:, 0]
-        hi_k = off2[:, -1] + len2[:, -1]
-        self.stats["posts"] += int((len2 > 0).sum())
+        if kept_k is None:
+            off2 = line_off.reshape(K, P)
+            len2 = line_len.reshape(K, P)
+            lo_k = off2[:, 0]
+            hi_k = off2[:, -1] + len2[:, -1]
+            self.stats["posts"] += int((len2 > 0).sum())
+        else:
+            # windowed: walker k owns the kept[k] lines from the
+            # exclusive cumsum of kept on; none = an empty range
+            end_k = np.cumsum(kept_k)
+            beg_k = end_k - kept_k
+            some = kept_k > 0
+            if len(line_off):
+                last = np.maximum(end_k - 1, 0)
+                lo_k = np.where(some, line_off[np.minimum(beg_k, last)], 0)
+                hi_k = np.where(some, line_off[last] + line_len[last], 0)
+            else:
+                lo_k = hi_k = np.zeros(K, dtype=np.int64)
+            self.stats["posts"] += int((line_len > 0).sum())
         items = [(p.url, int(lo_k[k]), int(hi_k[k]))
                  for k, p in enumerate(live) if hi_k[k] > lo_k[k]]
         # Random-walk allows REVISITS: if this hop touches a channel the
@@ -397,9 +486,10 @@ class GpuRandomWalk:
                 self.sm.wait_post_write(self._spill_tickets[other])
                 self._spill_tickets[other] = None
         self._inflight_paths[slot] = {u for u, _lo, _hi in items}
-        self._spill_tickets[slot] = self.sm.store_post_lines_batch(
-            items, memoryview(out_host.numpy()), ticket=True
-        )
+        if items:
+            self._spill_tickets[slot] = self.sm.store_post_lines_batch(
+                items, memoryview(out_host.numpy()), ticket=True
+            )
         self.timings["spill-issue"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
 
@@ -458,6 +548,15 @@ class GpuRandomWalk:
         self.timings["t-group"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
         for k, p in enumerate(live):
+            if active_k is not None and not active_k[k]:
+                # inactive channel = deadend (is_channel_active): no
+                # walk tail, so no edge and no next page; the chain
+                # ends here (RandomWalkRunner._process_page)
+                self.rw.mark_channel_crawled(p.url, 0)
+                self.rw.delete_pages([p.id])
+                self.stats["pages"] += 1
+                self.stats["deadends"] = self.stats.get("deadends", 0) + 1
+                continue
             try:
                 self._walk_tail_rows(
                     p, names_s[bounds[k]:bounds[k + 1]], hop_now)

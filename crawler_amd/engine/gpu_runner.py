@@ -31,6 +31,19 @@ row order, so the sample does not depend on chunk_channels. With none of
 the three flags set the window kernel is never launched and min_post_date
 stays a per-row filter inside parse+encode.
 
+Activity deadend: with --time-ago (ops.gpu.gate_params) the window kernel
+always runs (window_params(force=True)) and the channel gate
+(csrc/channel_gate.hip, the row form of is_channel_active) follows it: a
+channel whose newest fetched message, or whose newest message at all when
+nothing was fetched, is not newer than the cutoff is a deadend. It joins
+last_deadends, writes and truncates nothing, and none of its links is
+claimed. The kept rows then come from the compact-rows kernel. With
+--sample-size the newest FETCHED message is the newest of each path's own
+sample, so the CPU and the GPU crawl can disagree on a deadend exactly
+where their samples differ. --max-comments clamps the rows' comment counts
+(ops.gpu.cap_comments) before parse+encode, windowed or not. --min-users
+is not applied here.
+
 Cross-rank: ranks shard the layer's channels; newly-claimed hashes are
 all-gathered and merged into each rank's SeenSet (bench.py does the same
 per step) so a channel is crawled by exactly one rank per crawl.
@@ -111,6 +124,12 @@ class GpuCrawlEngine:
         # None = no fetch window: the per-row min_post_date filter of
         # parse+encode does everything
         window = self.gpu.window_params(self.cfg)
+        # --time-ago: the channel gate needs keep/kept, so the window
+        # kernel runs whatever else is set (force)
+        gate = self.gpu.gate_params(self.cfg)
+        if gate is not None:
+            window = self.gpu.window_params(self.cfg, force=True)
+        max_comments = getattr(self.cfg, "max_comments", -1)
         for ci, i in enumerate(range(0, len(ok), self.chunk_channels)):
             chunk = ok[i:i + self.chunk_channels]
             cids = np.array([c for _u, c in chunk], dtype=np.int64)
@@ -123,15 +142,31 @@ class GpuCrawlEngine:
                 # fetch window (date-between / max-posts / sample-size):
                 # only the kept rows are encoded, claimed and written
                 keep, kept = self.gpu.fetch_window(batch, **window)
+                if gate is not None:
+                    # activity deadend (is_channel_active): an inactive
+                    # channel loses its rows, so it writes no post, gets
+                    # no truncate and none of its links is claimed
+                    keep, kept, active, _latest = self.gpu.channel_gate(
+                        batch, keep, kept, **gate)
+                    for k in np.flatnonzero(active.cpu().numpy() == 0):
+                        self.last_deadends.add(chunk[k][0])
+                        self.stats["deadends"] += 1
                 kept_k = kept.cpu().numpy().astype(np.int64)
                 if not kept_k.any():
-                    # nothing of this chunk is inside the window: no
-                    # lines, no links, and no deadends either (below)
+                    # nothing of this chunk is kept: no lines, no links,
+                    # and no deadends beyond the gate's (recorded above)
                     self.stats["pages"] += len(chunk)
                     t["gen+kernels"] += _time.perf_counter() - t0
                     continue
                 from ..ops import batch as _B
-                batch = _B.select_rows(batch, keep.nonzero().flatten())
+                if gate is not None:
+                    rows, _row_channel = self.gpu.compact_rows(batch, keep,
+                                                               kept)
+                else:
+                    rows = keep.nonzero().flatten()
+                batch = _B.select_rows(batch, rows)
+            if max_comments is not None and max_comments >= 0:
+                batch = self.gpu.cap_comments(batch, max_comments)
             res = self.gpu.parse_encode(
                 batch, now=now, min_post_date=self.cfg.min_post_date
             )

@@ -14,7 +14,7 @@ CSRC = os.path.dirname(os.path.abspath(__file__)) + "/csrc"
 SOURCES = ["parse_encode.hip", "dedup.hip", "feedgen.hip", "yt_encode.hip",
            "yt_feedgen.hip", "yt_sample.hip", "yt_snowball.hip",
            "aggregate.hip", "htmlclass.hip", "sample.hip",
-           "fetch_window.hip"]
+           "fetch_window.hip", "channel_gate.hip"]
 OUT = os.path.join(CSRC, "libcrawlhip.so")
 
 

@@ -80,6 +80,11 @@ _SIGNATURES = {
     # fetch_window.hip
     "crawl_fetch_window": [_vp_t, _vp_t, _vp_t, _ci, _ci] + [_cl] * 5
                           + [_vp_t, _vp_t, _ci, _vp_t],
+    # channel_gate.hip
+    "crawl_channel_gate": [_vp_t, _vp_t, _ci, _ci, _cl] + [_vp_t] * 4
+                          + [_ci, _vp_t],
+    "crawl_compact_rows": [_vp_t, _vp_t, _ci, _ci, _vp_t, _vp_t, _ci,
+                           _vp_t],
     # yt_encode.hip
     "crawl_yt_ptr_count": [],
     "crawl_yt_measure": [_pp, _lp, _vp_t, _ci, _vp_t],
@@ -615,11 +620,15 @@ def fetch_window(batch: B.MessageBatch, stop_below: Optional[int] = None,
     return FetchWindowResult(keep, kept, raw_keep, raw_kept)
 
 
-def window_params(cfg) -> Optional[dict]:
+def window_params(cfg, force: bool = False) -> Optional[dict]:
     """The :func:`fetch_window` arguments a CrawlerConfig asks for, or
     None when the GPU crawl's per-row ``min_post_date`` filter already
     does all of it (no date-between window, no ``max_posts`` cap, no
-    sampling). Precedence is ``engine.pipeline.fetch_channel_messages``':
+    sampling). ``force=True`` never returns None: a caller that needs
+    ``keep`` and ``kept`` anyway (the channel gate, the random walk) gets
+    the walk that ``min_post_date`` alone stops, or one without bounds,
+    which is exactly the CPU walk's fetched set. Precedence is
+    ``engine.pipeline.fetch_channel_messages``':
     both date-between bounds set -> that window, ``min_post_date``
     ignored; otherwise ``min_post_date`` alone stops the walk. Sampling
     needs ``date_between_min`` (``_maybe_sample``). The CPU compares
@@ -639,11 +648,126 @@ def window_params(cfg) -> Optional[dict]:
     sample_k = (cfg.sample_size
                 if (cfg.sample_size and cfg.sample_size > 0
                     and cfg.date_between_min is not None) else 0)
-    if not window and cap == 0 and sample_k == 0:
+    if not force and not window and cap == 0 and sample_k == 0:
         return None
     return {"stop_below": stop, "skip_above": skip, "cap": int(cap),
             "sample_k": int(sample_k),
             "seed": int(getattr(cfg, "sample_seed", 0))}
+
+
+def gate_params(cfg) -> Optional[dict]:
+    """The :func:`channel_gate` cutoff a CrawlerConfig asks for
+    (``--time-ago``), or None without one. ``is_channel_active`` compares
+    integer dates with a float timestamp: ``d > ts`` is ``d > floor(ts)``."""
+    import math
+
+    if cfg.post_recency is None:
+        return None
+    return {"recency": math.floor(cfg.post_recency.timestamp())}
+
+
+def _grouped_shape(batch: B.MessageBatch, keep, kept):
+    """(K, P) of a K x P channel-grouped batch, after checking a
+    fetch-window result against it."""
+    dev = batch.device
+    K = batch.n_channels
+    P = batch.n // K if K else 0
+    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    for nm, t, dt_, n in (("keep", keep, torch.uint8, batch.n),
+                          ("kept", kept, torch.int32, K)):
+        assert t.dtype == dt_ and t.device == dev and t.is_contiguous(), nm
+        assert t.numel() == n, nm
+    return K, P
+
+
+def channel_gate(batch: B.MessageBatch, keep: torch.Tensor,
+                 kept: torch.Tensor, recency: int, *,
+                 _poison: Optional[int] = None):
+    """The activity deadend (``is_channel_active``) over a batch that
+    went through :func:`fetch_window` (csrc/channel_gate.hip; oracle:
+    golden_gate.channel_gate). A channel's newest date is the greatest
+    date of its kept rows, or, with none kept, the date of its row with
+    the greatest ``msg_id``; the channel is active iff that date is later
+    than ``recency`` (unix seconds; a tie is inactive). An inactive
+    channel loses its kept rows: ``keep`` and ``kept`` are updated IN
+    PLACE.
+
+    Returns ``(keep, kept, active uint8[K], latest int32[K])``. The kernel
+    writes every element of ``active`` and ``latest``; ``_poison`` (test
+    seam) fills both with that byte first. A batch without rows gives
+    all-inactive outputs and no launch."""
+    dev = batch.device
+    K, P = _grouped_shape(batch, keep, kept)
+    if _poison is None:
+        active = torch.empty(K, dtype=torch.uint8, device=dev)
+        latest = torch.empty(K, dtype=torch.int32, device=dev)
+    else:
+        active = torch.full((K,), _poison, dtype=torch.uint8, device=dev)
+        latest = torch.full((4 * K,), _poison, dtype=torch.uint8,
+                            device=dev).view(torch.int32)
+    if K == 0 or P == 0:
+        active.zero_()
+        latest.zero_()
+        return keep, kept, active, latest
+    from .golden_window import NO_SKIP, NO_STOP
+
+    recency = max(NO_STOP, min(NO_SKIP, int(recency)))
+    date = batch.meta["date"]
+    for nm, t, dt_ in (("date", date, torch.int32),
+                       ("msg_id", batch.msg_id, torch.int64)):
+        assert t.dtype == dt_ and t.device == dev and t.is_contiguous(), nm
+        assert t.numel() == batch.n, nm
+    _call("crawl_channel_gate", date, batch.msg_id, P, K, recency, keep,
+          kept, active, latest, min((K + 3) // 4, 8192))
+    return keep, kept, active, latest
+
+
+def compact_rows(batch: B.MessageBatch, keep: torch.Tensor,
+                 kept: torch.Tensor, *, _poison: Optional[int] = None):
+    """The kept rows of a windowed batch as indices
+    (csrc/channel_gate.hip; oracle: golden_gate.compact_rows): ``(rows
+    int64[sum(kept)], row_channel int32[sum(kept)])``, the global row
+    indices channel by channel and ascending within one, which is
+    ``keep.nonzero()``, and the channel each row belongs to. ``kept`` must
+    count the non-zero ``keep`` bytes per channel, as :func:`fetch_window`
+    and :func:`channel_gate` leave it; a channel's surplus rows would be
+    dropped, never written past its range. Nothing kept gives empty
+    outputs and no launch."""
+    dev = batch.device
+    K, P = _grouped_shape(batch, keep, kept)
+    kept_offset = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    if K:
+        if bool((kept < 0).any().item()):
+            raise ValueError("kept must not be negative")
+        torch.cumsum(kept, 0, dtype=torch.int64, out=kept_offset[1:])
+    total = int(kept_offset[-1].item())
+    if _poison is None:
+        rows = torch.empty(total, dtype=torch.int64, device=dev)
+        row_channel = torch.empty(total, dtype=torch.int32, device=dev)
+    else:
+        rows = torch.full((8 * total,), _poison, dtype=torch.uint8,
+                          device=dev).view(torch.int64)
+        row_channel = torch.full((4 * total,), _poison, dtype=torch.uint8,
+                                 device=dev).view(torch.int32)
+    if total == 0:
+        return rows, row_channel
+    _call("crawl_compact_rows", keep, kept_offset, P, K, rows, row_channel,
+          min((K + 3) // 4, 8192))
+    return rows, row_channel
+
+
+def cap_comments(batch: B.MessageBatch, max_comments: int):
+    """``--max-comments`` over a batch: a thread keeps its first
+    ``max_comments`` comments (``get_message_comments``), none with 0; a
+    negative value means no cap and returns the batch itself. Only the
+    rows' ``com_cnt`` column is replaced (clamped copy); the comment
+    table is shared and untouched, and parse+encode takes a thread's
+    length from ``com_cnt`` alone."""
+    if max_comments is None or max_comments < 0:
+        return batch
+    meta = dict(batch.meta)
+    meta["com_cnt"] = meta["com_cnt"].clamp(max=int(max_comments))
+    return dataclasses.replace(batch, meta=meta)
 
 
 _HTML_STATUS = ["valid", "not_channel", "invalid"]

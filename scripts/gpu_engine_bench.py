@@ -43,12 +43,22 @@ def main():
     ap.add_argument("--pipelined", action="store_true",
                     help="two half-pools: device stage overlaps host tail")
     ap.add_argument("--date-between-ts", default="",
-                    help="snowball: LO,HI unix seconds of a --date-between "
-                         "fetch window")
+                    help="snowball/randomwalk: LO,HI unix seconds of a "
+                         "--date-between fetch window")
     ap.add_argument("--max-posts", type=int, default=-1,
-                    help="snowball: --max-posts of the crawl")
+                    help="snowball/randomwalk: --max-posts of the crawl")
     ap.add_argument("--sample-size", type=int, default=0,
-                    help="snowball: --sample-size (with --date-between-ts)")
+                    help="snowball/randomwalk: --sample-size (with "
+                         "--date-between-ts)")
+    ap.add_argument("--time-ago-ts", type=float, default=None,
+                    help="snowball/randomwalk: unix seconds of the "
+                         "--time-ago cutoff (channels whose newest post "
+                         "is not newer are deadends)")
+    ap.add_argument("--max-comments", type=int, default=-1,
+                    help="snowball/randomwalk: --max-comments of the crawl")
+    ap.add_argument("--kernel-times", action="store_true",
+                    help="time every kernel launch with device events and "
+                         "report the sum per entry point")
     args = ap.parse_args()
 
     if args.mode == "randomwalk":
@@ -61,14 +71,9 @@ def main():
         sampling_method="snowball", max_depth=args.max_depth, min_users=1,
         max_pages=args.max_pages,
         skip_media_download=True,
-        max_posts=args.max_posts,
     )
-    if args.date_between_ts:
-        import datetime as dt
-        lo, hi = (float(x) for x in args.date_between_ts.split(","))
-        cfg.date_between_min = dt.datetime.fromtimestamp(lo, dt.timezone.utc)
-        cfg.date_between_max = dt.datetime.fromtimestamp(hi, dt.timezone.utc)
-        cfg.sample_size = args.sample_size
+    apply_fetch_flags(cfg, args)
+    kernel_ms = time_kernels() if args.kernel_times else None
     feed = SyntheticFeed(FeedConfig(seed=2026, universe=args.universe,
                                     posts_per_channel=args.posts))
     sm = LocalStateManager(cfg)
@@ -94,12 +99,73 @@ def main():
         "deadends": stats["deadends"],
         "max_depth": args.max_depth,
         "date_between_ts": args.date_between_ts or None,
-        "max_posts": args.max_posts,
-        "sample_size": args.sample_size,
     }
+    out.update(fetch_flags_echo(args))
     if getattr(eng, "timings", None):
         out["phase_s"] = {k: round(v, 3) for k, v in eng.timings.items()}
+    if kernel_ms is not None:
+        out["kernel_ms"] = kernel_ms()
     print(json.dumps(out))
+
+
+def apply_fetch_flags(cfg, args):
+    """The fetch and deadend flags of both modes onto the config."""
+    import datetime as dt
+
+    cfg.max_posts = args.max_posts
+    cfg.max_comments = args.max_comments
+    if args.date_between_ts:
+        lo, hi = (float(x) for x in args.date_between_ts.split(","))
+        cfg.date_between_min = dt.datetime.fromtimestamp(lo, dt.timezone.utc)
+        cfg.date_between_max = dt.datetime.fromtimestamp(hi, dt.timezone.utc)
+        cfg.sample_size = args.sample_size
+    if args.time_ago_ts is not None:
+        cfg.post_recency = dt.datetime.fromtimestamp(args.time_ago_ts,
+                                                     dt.timezone.utc)
+
+
+def fetch_flags_echo(args):
+    return {
+        "date_between_ts": args.date_between_ts or None,
+        "max_posts": args.max_posts,
+        "sample_size": args.sample_size,
+        "time_ago_ts": args.time_ago_ts,
+        "max_comments": args.max_comments,
+    }
+
+
+def time_kernels():
+    """Wrap ops.gpu._call so that every launch sits between two device
+    events on its stream. Returns a function that gives {entry point:
+    [launches, total ms]} once the crawl is over."""
+    import torch
+
+    from crawler_amd.ops import gpu
+
+    real, spans = gpu._call, []
+
+    def timed(name, *a, stream=None, **kw):
+        st = stream or torch.cuda.current_stream()
+        beg = torch.cuda.Event(enable_timing=True)
+        end = torch.cuda.Event(enable_timing=True)
+        beg.record(st)
+        try:
+            return real(name, *a, stream=stream, **kw)
+        finally:
+            end.record(st)
+            spans.append((name, beg, end))
+
+    gpu._call = timed
+
+    def report():
+        torch.cuda.synchronize()
+        out = {}
+        for name, beg, end in spans:
+            n, ms = out.get(name, (0, 0.0))
+            out[name] = (n + 1, ms + beg.elapsed_time(end))
+        return {k: [n, round(ms, 3)] for k, (n, ms) in sorted(out.items())}
+
+    return report
 
 
 def run_randomwalk(args):
@@ -115,6 +181,8 @@ def run_randomwalk(args):
         sampling_method="random-walk", min_users=1,
         walkback_rate=args.walkback_rate, skip_media_download=True,
     )
+    apply_fetch_flags(cfg, args)
+    kernel_ms = time_kernels() if args.kernel_times else None
     feed = SyntheticFeed(FeedConfig(seed=2027, universe=args.universe,
                                     posts_per_channel=args.posts))
     sm = LocalStateManager(cfg)
@@ -126,7 +194,7 @@ def run_randomwalk(args):
     stats = eng.run(max_pages=args.max_pages,
                     pipelined=bool(args.pipelined))
     elapsed = time.perf_counter() - t0
-    print(json.dumps({
+    out = {
         "metric": "random-walk posts/sec (batched hops incl. disk)",
         "value": round(stats["posts"] / elapsed, 1),
         "elapsed_s": round(elapsed, 2),
@@ -135,6 +203,7 @@ def run_randomwalk(args):
         "posts": stats["posts"],
         "edges": stats["edges"],
         "walkback_exhausted": stats["walkback_exhausted"],
+        "deadends": stats["deadends"],
         "phase_s": {k: round(v, 3) for k, v in eng.timings.items()},
         "per_hop": [
             {"pages": h[0], "posts": h[1],
@@ -142,7 +211,11 @@ def run_randomwalk(args):
              "s": h[2], "phases": (h[3] if len(h) > 3 else {})}
             for h in eng.hop_log
         ],
-    }))
+    }
+    out.update(fetch_flags_echo(args))
+    if kernel_ms is not None:
+        out["kernel_ms"] = kernel_ms()
+    print(json.dumps(out))
 
 
 def run_media(args):
