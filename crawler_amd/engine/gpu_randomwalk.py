@@ -14,16 +14,16 @@ it decodes to a universe id (the SearchPublicChat equivalent — the live
 check the reference does at crawl/runner.go:1310-1383) and passes
 FilterUsername and the invalid-channel cache.
 
-Fetch and deadend flags: with --date-between, --max-posts, --sample-size,
---min-post-date, --time-ago or --max-comments set, a hop runs the fetch
-window, the channel gate and the compact-rows kernel (ops.gpu) before
-parse+encode, as the BFS engine does (engine/gpu_runner.py): a walker then
-owns kept[k] rows, not P, and the walker of a link comes from the
-compaction's row-to-walker map. An active walker without a kept row
-writes nothing and walks back; an inactive one is a deadend: its page is
-counted and deleted, and its chain ends. With none of the flags set a hop
-launches what it always did. --min-users, --tandem-crawl and
---max-crawl-duration are not applied here.
+Fetch and deadend flags: engine/gpu_stage.py states the rules and holds
+the stage (FetchStage). The walk forces the window for --min-post-date and
+--max-comments too, so the window applies min_post_date as the CPU walk
+does and parse+encode gets no date filter. A walker then owns kept[k]
+rows, not P, and the walker of a link comes from the compaction's
+row-to-walker map. An active walker without a kept row writes nothing and
+walks back; an inactive one is a deadend: its page is counted and deleted,
+and its chain ends. With none of the flags set a hop launches what it
+always did. --min-users, --tandem-crawl and --max-crawl-duration are not
+applied here.
 """
 from __future__ import annotations
 
@@ -36,6 +36,8 @@ import torch
 
 from ..feed.synth import SyntheticFeed
 from . import randomwalk, vecvalidate
+from .gpu_stage import (FetchStage, SpillRing, channel_ranges, cid_of,
+                        comment_cap, padded_name_rows)
 from .state import LocalStateManager, Page, RandomWalkStore
 
 
@@ -58,10 +60,13 @@ class GpuRandomWalk:
         self.seen = gpu_mod.SeenSet(self.device)
         self.stats = {"pages": 0, "posts": 0, "invalid_400": 0,
                       "walkback_exhausted": 0, "edges": 0, "deadends": 0}
-        self._pin_ring = [None, None]       # pinned host JSONL slots
-        self._spill_tickets = [None, None]  # native-sink tickets
+        # the walk needs keep/kept for any fetch flag, not only for the
+        # ones that make a window of their own
+        self.fetch = FetchStage(
+            gpu_mod, cfg, force_window=(cfg.min_post_date is not None
+                                        or comment_cap(cfg) is not None))
+        self.spill = SpillRing(sm)
         self._inflight_paths = {}           # slot -> channel set
-        self._hop_idx = 0
         # cross-hop validation cache keyed by link hash — a vectorized
         # open-addressing table (linear probe, power-of-two size):
         # validation is a pure function of the name, so hits skip
@@ -83,13 +88,6 @@ class GpuRandomWalk:
                 id=str(uuid.uuid4()), url=u, depth=0,
                 sequence_id=str(uuid.uuid4()), status="unfetched",
             ))
-
-    def _cid_of(self, username: str) -> Optional[int]:
-        if username.startswith("c") and username[1:].isdigit():
-            cid = int(username[1:])
-            if cid < self.feed.cfg.universe:
-                return cid
-        return None
 
     def _inv_snapshot(self, now, width: int):
         """Sorted S<width> snapshot of the live (non-expired) invalid
@@ -227,8 +225,7 @@ class GpuRandomWalk:
         live = self._claim_400(pages)
         if not live:
             return 0
-        slot = self._ring_slot()
-        payload = self._hop_gpu(live, slot, now)
+        payload = self._hop_gpu(live, self.spill.claim(), now)
         self._hop_host(live, payload)
         return len(live)
 
@@ -237,7 +234,7 @@ class GpuRandomWalk:
         (host-side; consumes rng, so it stays on the main thread)."""
         live: List[Page] = []
         for p in pages:
-            if self._cid_of(p.url) is None:
+            if cid_of(p.url, self.feed.cfg.universe) is None:
                 self.stats["invalid_400"] += 1
                 try:
                     randomwalk.handle_400_replacement(
@@ -250,16 +247,6 @@ class GpuRandomWalk:
                 live.append(p)
         return live
 
-    def _ring_slot(self) -> int:
-        """Claim the next pinned-ring slot and retire its old spill
-        ticket. MAIN THREAD ONLY: the native sink's ticket wait also
-        evicts surplus fds and must not race a concurrent submit."""
-        slot = self._hop_idx % 2
-        self._hop_idx += 1
-        self.sm.wait_post_write(self._spill_tickets[slot])
-        self._spill_tickets[slot] = None
-        return slot
-
     def _hop_gpu(self, live: List[Page], slot: int,
                  now: Optional[_dt.datetime] = None) -> dict:
         """Device stage: feedgen -> (with a fetch or deadend flag: fetch
@@ -271,37 +258,22 @@ class GpuRandomWalk:
         now = now or _dt.datetime.now(_dt.timezone.utc)
         import time as _time
         t0 = _time.perf_counter()
-        cids = np.array([self._cid_of(p.url) for p in live],
-                        dtype=np.int64)
+        cids = np.array([cid_of(p.url, self.feed.cfg.universe)
+                         for p in live], dtype=np.int64)
         batch = self.feed.build_batch_device(
             cids, self.device, posts_per_channel=self.ppc
         )
         torch.cuda.synchronize()
         self.timings["feedgen"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
-        fetch = self._fetch_flags()
-        kept_k = active_k = row_channel = None
-        if fetch is not None:
-            # fetch window -> activity gate -> kept rows: a walker owns
-            # kept[k] rows, not P, so the row-to-walker map travels with
-            # the rows (row_channel). The window applies min_post_date
-            # as the CPU walk does, so parse+encode gets no date filter.
-            window, gate, max_comments = fetch
-            keep, kept = self.gpu.fetch_window(batch, **window)
-            if gate is not None:
-                keep, kept, active, _latest = self.gpu.channel_gate(
-                    batch, keep, kept, **gate)
-                active_k = active.cpu().numpy() != 0
-            rows, row_channel = self.gpu.compact_rows(batch, keep, kept)
-            kept_k = kept.cpu().numpy().astype(np.int64)
-            if rows.numel() == 0:
-                # no walker kept a row: nothing to encode, claim or
-                # copy; the host tails still run (walk back / deadend)
-                self.timings["kernels"] += _time.perf_counter() - t0
-                return self._empty_payload(slot, now, kept_k, active_k)
-            from ..ops import batch as _B
-            batch = self.gpu.cap_comments(_B.select_rows(batch, rows),
-                                          max_comments)
+        # windowed, a walker owns kept[k] rows, not P, so the row-to-walker
+        # map travels with the rows (row_channel)
+        batch, kept_k, active_k, row_channel = self.fetch.apply(batch)
+        if batch is None:
+            # no walker kept a row: nothing to encode, claim or
+            # copy; the host tails still run (walk back / deadend)
+            self.timings["kernels"] += _time.perf_counter() - t0
+            return self._empty_payload(slot, now, kept_k, active_k)
         res = self.gpu.parse_encode(batch, now=now)
         self.seen.claim(res)
         torch.cuda.synchronize()
@@ -334,11 +306,8 @@ class GpuRandomWalk:
         # name dedup AND pre-sorted per-walker output: the host's
         # per-walker sorted() over ~300-name lists disappears, and the
         # cross-hop cache's hash keying no longer decides dedup.
-        col = torch.arange(w, device=dev, dtype=lens_g.dtype)
-        all_lens = lens_g[mi_g, si_g]
-        all_rows = torch.where(col[None, :] < all_lens[:, None],
-                               names_g[mi_g, si_g],
-                               torch.zeros_like(names_g[mi_g, si_g]))
+        all_rows = padded_name_rows(names_g[mi_g, si_g],
+                                    lens_g[mi_g, si_g])
         be = (256 ** torch.arange(7, -1, -1, device=dev,
                                   dtype=torch.int64))
         keys = (all_rows.view(-1, 4, 8).to(torch.int64) * be).sum(-1)
@@ -377,14 +346,7 @@ class GpuRandomWalk:
         u_rows = u_rows_g.cpu().numpy()
         ok_all = ok_g.cpu().numpy()
         cid_ok_all = cid_ok_g.cpu().numpy()
-        need = int(res.out.numel())
-        ring = self._pin_ring
-        if ring[slot] is None or ring[slot].numel() < need:
-            ring[slot] = torch.empty(need + need // 8,
-                                     dtype=torch.uint8,
-                                     pin_memory=True)
-        out_host = ring[slot][:need]
-        out_host.copy_(res.out, non_blocking=True)
+        out_host = self.spill.stage(slot, res.out)
         ev = torch.cuda.Event()
         ev.record()
         self.timings["d2h"] += _time.perf_counter() - t0
@@ -394,23 +356,6 @@ class GpuRandomWalk:
                 "u_rows": u_rows, "ok_all": ok_all,
                 "cid_ok_all": cid_ok_all, "w": w, "now": now,
                 "kept_k": kept_k, "active_k": active_k}
-
-    def _fetch_flags(self):
-        """None when no fetch or deadend flag is set (the hop then
-        launches what it always did), else ``(window, gate,
-        max_comments)``: the fetch_window arguments (forced: the walk
-        needs keep/kept whatever the flag), the channel_gate arguments
-        or None, and the comment cap (negative = none)."""
-        cfg = self.cfg
-        max_comments = getattr(cfg, "max_comments", -1)
-        if max_comments is None:
-            max_comments = -1
-        gate = self.gpu.gate_params(cfg)
-        if (self.gpu.window_params(cfg) is None and gate is None
-                and cfg.min_post_date is None and max_comments < 0):
-            return None
-        return (self.gpu.window_params(cfg, force=True), gate,
-                max_comments)
 
     @staticmethod
     def _empty_payload(slot: int, now, kept_k, active_k) -> dict:
@@ -443,7 +388,6 @@ class GpuRandomWalk:
         ok_all = payload["ok_all"]
         cid_ok_all = payload["cid_ok_all"]
         w = payload["w"]
-        P = self.ppc
         kept_k = payload.get("kept_k")
         active_k = payload.get("active_k")
         if payload["ev"] is not None:
@@ -454,42 +398,21 @@ class GpuRandomWalk:
 
         # spill JSONL per channel (K x P layout) in ONE native-sink call
         K = len(live)
-        if kept_k is None:
-            off2 = line_off.reshape(K, P)
-            len2 = line_len.reshape(K, P)
-            lo_k = off2[:, 0]
-            hi_k = off2[:, -1] + len2[:, -1]
-            self.stats["posts"] += int((len2 > 0).sum())
-        else:
-            # windowed: walker k owns the kept[k] lines from the
-            # exclusive cumsum of kept on; none = an empty range
-            end_k = np.cumsum(kept_k)
-            beg_k = end_k - kept_k
-            some = kept_k > 0
-            if len(line_off):
-                last = np.maximum(end_k - 1, 0)
-                lo_k = np.where(some, line_off[np.minimum(beg_k, last)], 0)
-                hi_k = np.where(some, line_off[last] + line_len[last], 0)
-            else:
-                lo_k = hi_k = np.zeros(K, dtype=np.int64)
-            self.stats["posts"] += int((line_len > 0).sum())
+        lo_k, hi_k, n_lines_k = channel_ranges(line_off, line_len, K,
+                                               self.ppc, kept_k)
+        self.stats["posts"] += int(n_lines_k.sum())
         items = [(p.url, int(lo_k[k]), int(hi_k[k]))
                  for k, p in enumerate(live) if hi_k[k] > lo_k[k]]
         # Random-walk allows REVISITS: if this hop touches a channel the
         # other in-flight batch is still appending to, wait it out first
         # so a channel's posts never interleave mid-line (the CPU path
         # appends visits strictly in order).
-        other = 1 - slot
-        if self._spill_tickets[other] is not None:
-            mine = {u for u, _lo, _hi in items}
-            if mine & self._inflight_paths.get(other, set()):
-                self.sm.wait_post_write(self._spill_tickets[other])
-                self._spill_tickets[other] = None
-        self._inflight_paths[slot] = {u for u, _lo, _hi in items}
+        mine = {u for u, _lo, _hi in items}
+        if mine & self._inflight_paths.get(1 - slot, set()):
+            self.spill.wait(1 - slot)
+        self._inflight_paths[slot] = mine
         if items:
-            self._spill_tickets[slot] = self.sm.store_post_lines_batch(
-                items, memoryview(out_host.numpy()), ticket=True
-            )
+            self.spill.submit(slot, items, memoryview(out_host.numpy()))
         self.timings["spill-issue"] += _time.perf_counter() - t0
         t0 = _time.perf_counter()
 
@@ -636,10 +559,7 @@ class GpuRandomWalk:
             self._run_pipelined(max_pages, now)
         else:
             self._run_serial(max_pages, now)
-        for slot in (0, 1):
-            self.sm.wait_post_write(self._spill_tickets[slot])
-            self._spill_tickets[slot] = None
-        self.sm.drain_post_writes()
+        self.spill.drain()
         self.sm.save_state()
         self.sm.close()
         return dict(self.stats)
@@ -684,8 +604,8 @@ class GpuRandomWalk:
                 live = self._claim_400(pages) if pages else []
                 fut = None
                 if live:
-                    slot = self._ring_slot()
-                    fut = ex.submit(self._hop_gpu, live, slot, now)
+                    fut = ex.submit(self._hop_gpu, live,
+                                    self.spill.claim(), now)
                 processed = pending is not None
                 if processed:
                     plive, pfut = pending

@@ -15,34 +15,12 @@ Equivalence contract: for the same channels the JSONL bytes are identical
 to the CPU pipeline's Post.to_jsonl() output (enforced by the byte-exact
 kernel tests) and the discovered-channel set matches golden extraction.
 
-Fetch window: with --date-between, --max-posts or --sample-size set
-(ops.gpu.window_params), a chunk first goes through the fetch-window
-kernel (csrc/fetch_window.hip), the row form of fetch_channel_messages'
-walk, and only the kept rows (batch.select_rows) are encoded, claimed and
-written; a channel then owns kept[k] lines, not P, and one with no kept
-row writes and truncates nothing. Without sampling the kept set is the
-CPU path's. With --sample-size the two paths agree in the sample's size,
-in drawing a uniform subset of the same window and in being
-deterministic, but not in WHICH posts are drawn or in their order: the
-CPU path shuffles with Python's random (Fisher-Yates) and writes the
-sample in shuffled order; this path keeps the sample_size smallest
-splitmix64 keys of (--sample-seed, chat_id, msg_id) and writes them in
-row order, so the sample does not depend on chunk_channels. With none of
-the three flags set the window kernel is never launched and min_post_date
-stays a per-row filter inside parse+encode.
-
-Activity deadend: with --time-ago (ops.gpu.gate_params) the window kernel
-always runs (window_params(force=True)) and the channel gate
-(csrc/channel_gate.hip, the row form of is_channel_active) follows it: a
-channel whose newest fetched message, or whose newest message at all when
-nothing was fetched, is not newer than the cutoff is a deadend. It joins
-last_deadends, writes and truncates nothing, and none of its links is
-claimed. The kept rows then come from the compact-rows kernel. With
---sample-size the newest FETCHED message is the newest of each path's own
-sample, so the CPU and the GPU crawl can disagree on a deadend exactly
-where their samples differ. --max-comments clamps the rows' comment counts
-(ops.gpu.cap_comments) before parse+encode, windowed or not. --min-users
-is not applied here.
+Fetch and deadend flags: engine/gpu_stage.py states the rules and holds
+the stage (FetchStage). This engine never forces the window: with none of
+--date-between, --max-posts, --sample-size and --time-ago set the window
+kernel is never launched, and min_post_date is always a per-row filter
+inside parse+encode as well. An inactive channel joins last_deadends.
+--min-users is not applied here.
 
 Cross-rank: ranks shard the layer's channels; newly-claimed hashes are
 all-gathered and merged into each rank's SeenSet (bench.py does the same
@@ -58,6 +36,8 @@ import torch
 
 from ..feed.synth import SyntheticFeed
 from ..parallel import collectives as C
+from .gpu_stage import (FetchStage, SpillRing, channel_ranges, cid_of,
+                        padded_name_rows)
 from .state import LocalStateManager, Page
 
 
@@ -80,22 +60,15 @@ class GpuCrawlEngine:
         # pin the capture timestamp for byte-reproducible crawls
         # (tools/verify_jsonl.py re-derives expected bytes from it)
         self.fixed_now = fixed_now
-        self._pin_ring = [None, None]      # reusable pinned host slots
-        self._spill_tickets = [None, None]  # sink ticket per ring slot
+        # None window = the per-row min_post_date filter of parse+encode
+        # does everything
+        self.fetch = FetchStage(gpu_mod, cfg, force_window=False)
+        self.spill = SpillRing(sm)
         import collections
         self.timings = collections.defaultdict(float)  # phase seconds
         self.stats = {"pages": 0, "posts": 0, "jsonl_bytes": 0,
                       "discovered": 0, "deadends": 0}
         self.last_deadends = set()
-
-    # ---- helpers ----
-
-    def _cid_of(self, username: str) -> Optional[int]:
-        if username.startswith("c") and username[1:].isdigit():
-            cid = int(username[1:])
-            if cid < self.feed.cfg.universe:
-                return cid
-        return None
 
     def process_channels(self, usernames: List[str],
                          now: Optional[_dt.datetime] = None,
@@ -112,7 +85,8 @@ class GpuCrawlEngine:
         posts_total = 0
         t = self.timings
         import time as _time
-        valid = [(u, self._cid_of(u)) for u in usernames]
+        universe = self.feed.cfg.universe
+        valid = [(u, cid_of(u, universe)) for u in usernames]
         bad = [u for u, c in valid if c is None]
         ok = [(u, c) for u, c in valid if c is not None]
         # deadend channels of THIS call (invalid username or zero posts
@@ -121,52 +95,24 @@ class GpuCrawlEngine:
         self.last_deadends = set(bad)
         for u in bad:
             self.stats["deadends"] += 1
-        # None = no fetch window: the per-row min_post_date filter of
-        # parse+encode does everything
-        window = self.gpu.window_params(self.cfg)
-        # --time-ago: the channel gate needs keep/kept, so the window
-        # kernel runs whatever else is set (force)
-        gate = self.gpu.gate_params(self.cfg)
-        if gate is not None:
-            window = self.gpu.window_params(self.cfg, force=True)
-        max_comments = getattr(self.cfg, "max_comments", -1)
-        for ci, i in enumerate(range(0, len(ok), self.chunk_channels)):
+        for i in range(0, len(ok), self.chunk_channels):
             chunk = ok[i:i + self.chunk_channels]
             cids = np.array([c for _u, c in chunk], dtype=np.int64)
             t0 = _time.perf_counter()
             batch = self.feed.build_batch_device(
                 cids, self.device, posts_per_channel=self.ppc
             )
-            kept_k = None
-            if window is not None:
-                # fetch window (date-between / max-posts / sample-size):
-                # only the kept rows are encoded, claimed and written
-                keep, kept = self.gpu.fetch_window(batch, **window)
-                if gate is not None:
-                    # activity deadend (is_channel_active): an inactive
-                    # channel loses its rows, so it writes no post, gets
-                    # no truncate and none of its links is claimed
-                    keep, kept, active, _latest = self.gpu.channel_gate(
-                        batch, keep, kept, **gate)
-                    for k in np.flatnonzero(active.cpu().numpy() == 0):
-                        self.last_deadends.add(chunk[k][0])
-                        self.stats["deadends"] += 1
-                kept_k = kept.cpu().numpy().astype(np.int64)
-                if not kept_k.any():
-                    # nothing of this chunk is kept: no lines, no links,
-                    # and no deadends beyond the gate's (recorded above)
-                    self.stats["pages"] += len(chunk)
-                    t["gen+kernels"] += _time.perf_counter() - t0
-                    continue
-                from ..ops import batch as _B
-                if gate is not None:
-                    rows, _row_channel = self.gpu.compact_rows(batch, keep,
-                                                               kept)
-                else:
-                    rows = keep.nonzero().flatten()
-                batch = _B.select_rows(batch, rows)
-            if max_comments is not None and max_comments >= 0:
-                batch = self.gpu.cap_comments(batch, max_comments)
+            batch, kept_k, active_k, _row_channel = self.fetch.apply(batch)
+            if active_k is not None:
+                for k in np.flatnonzero(~active_k):
+                    self.last_deadends.add(chunk[k][0])
+                    self.stats["deadends"] += 1
+            if batch is None:
+                # nothing of this chunk is kept: no lines, no links,
+                # and no deadends beyond the gate's (recorded above)
+                self.stats["pages"] += len(chunk)
+                t["gen+kernels"] += _time.perf_counter() - t0
+                continue
             res = self.gpu.parse_encode(
                 batch, now=now, min_post_date=self.cfg.min_post_date
             )
@@ -177,49 +123,18 @@ class GpuCrawlEngine:
             # host spill: per-channel JSONL slices. Messages are grouped
             # by channel (K x P layout), so channel k owns lines
             # [k*P, (k+1)*P) -> bytes [line_off[kP], line_off[(k+1)P-1]+len).
-            # The pinned HOST RING (2 slots, allocated once) replaces a
-            # per-chunk 1GB pin_memory allocation (which cost ~0.1s/chunk
-            # — the d2h phase was allocation-bound, not copy-bound); the
-            # slot's previous SINK TICKET is awaited before the D2H may
-            # overwrite it, making the spill pipeline 2 chunks deep.
-            slot = ci % 2
-            self.sm.wait_post_write(self._spill_tickets[slot])
-            self._spill_tickets[slot] = None
-            need = int(res.out.numel())
-            ring = self._pin_ring
-            if ring[slot] is None or ring[slot].numel() < need:
-                ring[slot] = torch.empty(need + need // 8,
-                                         dtype=torch.uint8,
-                                         pin_memory=True)
-            out_host = ring[slot][:need]
-            out_host.copy_(res.out, non_blocking=True)
+            # Through the pinned spill ring (gpu_stage.SpillRing), which
+            # makes the spill pipeline 2 chunks deep.
+            slot = self.spill.claim()
+            out_host = self.spill.stage(slot, res.out)
             line_off = res.line_off.cpu().numpy()
             line_len = res.line_len.cpu().numpy()
             torch.cuda.synchronize()
             t["d2h"] += _time.perf_counter() - t0; t0 = _time.perf_counter()
             buf = memoryview(out_host.numpy())
-            P = self.ppc
             K = len(chunk)
-            # vectorized per-channel ranges/counts (a python loop over
-            # numpy scalars costs ~0.3s per 1500 channels)
-            if kept_k is None:
-                off2 = line_off.reshape(K, P)
-                len2 = line_len.reshape(K, P)
-                lo_k = off2[:, 0]
-                hi_k = off2[:, -1] + len2[:, -1]
-                n_lines_k = (len2 > 0).sum(axis=1)
-            else:
-                # windowed: channel k owns the kept[k] lines from the
-                # exclusive cumsum of kept on; none = an empty range
-                end_k = np.cumsum(kept_k)
-                beg_k = end_k - kept_k
-                some = kept_k > 0
-                last = np.maximum(end_k - 1, 0)
-                lo_k = np.where(some, line_off[np.minimum(beg_k, last)], 0)
-                hi_k = np.where(some, line_off[last] + line_len[last], 0)
-                written = np.concatenate(
-                    ([0], np.cumsum(line_len > 0, dtype=np.int64)))
-                n_lines_k = written[end_k] - written[beg_k]
+            lo_k, hi_k, n_lines_k = channel_ranges(line_off, line_len, K,
+                                                   self.ppc, kept_k)
             posts_total += int(n_lines_k.sum())
             self.stats["pages"] += K
             items = []
@@ -235,14 +150,8 @@ class GpuCrawlEngine:
                 # reference only deadends on inactivity/zero-message/
                 # min-users (runner.go:635) — synthetic channels always
                 # have messages, so only invalid usernames deadend here
-            # one fan-out call for the whole chunk: the native sink
-            # (crawler_amd/native) appends all channels in parallel with
-            # the GIL released; the ticket is awaited when this ring slot
-            # comes around again (2-deep: chunk i's disk writes run under
-            # chunks i+1 AND i+2's GPU work).
-            self._spill_tickets[slot] = self.sm.store_post_lines_batch(
-                items, buf, ticket=True
-            )
+            # the ticket is awaited when this ring slot comes around again
+            self.spill.submit(slot, items, buf)
             self.stats["jsonl_bytes"] += int(buf.shape[0])
             t["spill"] += _time.perf_counter() - t0; t0 = _time.perf_counter()
 
@@ -265,14 +174,7 @@ class GpuCrawlEngine:
                     names_g = res.link_name[rows, cols]
                     lens_g = res.link_len[rows, cols]
                     w = names_g.shape[1]
-                    # zero-pad ON THE GPU so the D2H ships clean
-                    # fixed-width byte strings
-                    col_idx = torch.arange(w, device=names_g.device,
-                                           dtype=lens_g.dtype)
-                    padded_g = torch.where(
-                        col_idx[None, :] < lens_g[:, None], names_g,
-                        torch.zeros_like(names_g))
-                    padded = padded_g.cpu().numpy()
+                    padded = padded_name_rows(names_g, lens_g).cpu().numpy()
                     lens = lens_g.cpu().numpy()
                     blob = padded.tobytes().decode("ascii", "replace")
                     discovered.extend(
@@ -300,10 +202,7 @@ class GpuCrawlEngine:
         """Wait out all in-flight ticketed sink writes (safe point for
         save_state; truncate-then-write keeps re-processing
         exactly-once if a crash lands before this)."""
-        for slot in (0, 1):
-            self.sm.wait_post_write(self._spill_tickets[slot])
-            self._spill_tickets[slot] = None
-        self.sm.drain_post_writes()
+        self.spill.drain()
 
     # ---- BFS crawl (snowball / channel) ----
 

@@ -292,6 +292,7 @@ def test_comment_cap_matches_run_for_channel(tmp_path, max_comments):
 
 def mk_walk(tmp_path):
     from crawler_amd.engine.gpu_randomwalk import GpuRandomWalk
+    from crawler_amd.engine.gpu_stage import SpillRing
     import collections
 
     cfg = CrawlerConfig(crawl_id="gw1", storage_root=str(tmp_path),
@@ -306,7 +307,7 @@ def mk_walk(tmp_path):
     g.stats = {"pages": 0, "posts": 0, "invalid_400": 0,
                "walkback_exhausted": 0, "edges": 0, "deadends": 0}
     g.timings = collections.defaultdict(float)
-    g._spill_tickets = [None, None]
+    g.spill = SpillRing(g.sm)
     g._inflight_paths = {}
     g._vc_init(1 << 8)
     for i in range(100, 130):
@@ -369,9 +370,7 @@ def test_walk_host_windowed_ranges(tmp_path):
         "active_k": np.array([True, False, True]),
     }
     g._hop_host(live, payload)
-    for slot in (0, 1):
-        g.sm.wait_post_write(g._spill_tickets[slot])
-    g.sm.drain_post_writes()
+    g.spill.drain()
     g.sm.close()
     read = lambda p: (tmp_path / "gw1" / p.url / "posts"
                       / "posts.jsonl")

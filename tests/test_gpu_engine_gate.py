@@ -280,3 +280,36 @@ def test_without_a_flag_nothing_new_is_launched(tmp_path, monkeypatch):
             lines[k * P:(k + 1) * P]), f"channel {cid} JSONL differs"
     assert set(discovered) == {n for row in links for (n, _s) in row}
     assert posts == 3 * P and eng.last_deadends == set()
+
+
+def test_max_posts_alone_compacts_its_rows_on_the_device(tmp_path,
+                                                         monkeypatch):
+    """A window without a gate takes its kept rows from the compact-rows
+    kernel too, over more than one chunk."""
+    from crawler_amd.ops import gpu
+
+    feed = mk_feed()
+    cids, _cutoff, _tie = split_channels(feed, P)
+    assert len(cids) == 6
+    real, launched = gpu._call, []
+
+    def spy(name, *args, **kwargs):
+        launched.append(name)
+        return real(name, *args, **kwargs)
+
+    monkeypatch.setattr(gpu, "_call", spy)
+    cfg, sm, eng = mk_engine(tmp_path, feed, chunk_channels=4, max_posts=9)
+    assert gpu.gate_params(cfg) is None
+    names = ["c%010d" % c for c in cids]
+    discovered, posts = eng.process_channels(names, now=NOW)
+    sm.close()
+    assert launched.count("crawl_fetch_window") == 2
+    assert launched.count("crawl_compact_rows") == 2
+    assert "crawl_channel_gate" not in launched
+    files, link_names, _active = expectation(feed, cfg, cids)
+    for k, cid in enumerate(cids):
+        assert files[k].count(b"\n") == 9
+        assert read_posts(tmp_path, "g1", cid) == files[k], f"channel {cid}"
+    assert set(discovered) == link_names
+    assert posts == 6 * 9 and eng.stats["posts"] == 6 * 9
+    assert eng.stats["pages"] == 6 and eng.last_deadends == set()

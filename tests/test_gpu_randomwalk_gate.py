@@ -225,7 +225,8 @@ def test_without_a_flag_nothing_new_is_launched(tmp_path, monkeypatch):
 
     monkeypatch.setattr(gpu, "_call", spy)
     cfg, sm, rw, eng = mk(tmp_path, feed)
-    assert eng._fetch_flags() is None
+    assert (eng.fetch.window is None and eng.fetch.gate is None
+            and eng.fetch.max_comments is None)
     names = ["c%010d" % c for c in CIDS]
     eng.seed(names)
     stats = eng.run(max_pages=len(CIDS), now=NOW)
