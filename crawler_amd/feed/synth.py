@@ -355,13 +355,6 @@ class SyntheticFeed:
         self._dev_tables[key] = tables
         return tables
 
-    _TBL_ORDER = [
-        "pool", "pool_off", "pool_len", "text_len", "ctype", "tflags",
-        "aux", "aux_off", "aux_len", "ents", "ent_off", "ent_cnt",
-        "slots", "slot_off", "slot_cnt", "cdf", "ctext", "ctext_off",
-        "ctext_len",
-    ]
-
     def build_batch_device(self, channel_ids: np.ndarray, device,
                            posts_per_channel: Optional[int] = None
                            ) -> B.MessageBatch:
@@ -370,6 +363,7 @@ class SyntheticFeed:
         import torch as T
 
         from ..ops import gpu as gpu_mod
+        from ..ops import views
 
         cfg = self.cfg
         P = posts_per_channel or cfg.posts_per_channel
@@ -388,8 +382,7 @@ class SyntheticFeed:
             return self.build_batch(
                 np.zeros(0, dtype=np.int64), P).to(device)
         tables = self._device_tables(device)
-        tbl_ptrs = gpu_mod._ptr_array(
-            [tables[name] for name in self._TBL_ORDER])
+        tbl_ptrs = views.bind("TemplateTables", tables.get, device)
         scalars = (ctypes.c_long * 10)(
             len(self.templates), len(self._comment_bytes), cfg.seed,
             cfg.universe, cfg.base_date, cfg.date_step, int(permille),
@@ -403,30 +396,18 @@ class SyntheticFeed:
         chat_id, msg_id, block_len = z64(N), z64(N), z64(N)
         m = {f: z32(N) for f in B._META_FIELDS_I32}
         tidx = z32(N)
-        out_ptrs = gpu_mod._ptr_array([
-            chat_id, msg_id, m["date"], m["content_type"], m["views"],
-            m["forwards"], m["media_album_id"], m["channel_idx"],
-            m["flags"], m["text_len"], m["aux_len"], m["ent_cnt"],
-            m["react_cnt"], m["com_cnt"], m["poster_len"],
-            m["reply_count"], block_len, tidx,
-        ])
+        # every output list: the meta column of that name, else a local
+        out_ptrs = views.bind("FeedMetaOut", dict(
+            m, chat_id=chat_id, msg_id=msg_id, block_len=block_len,
+            tidx=tidx).get, device)
         grid = min((N + 255) // 256, 8192)
         gpu_mod._call("crawl_feed_meta", tbl_ptrs, scalars, cids_t, out_ptrs,
                       grid)
 
-        def excl_cumsum(x64):
-            out = T.zeros(x64.numel() + 1, dtype=T.int64, device=device)
-            T.cumsum(x64, 0, out=out[1:])
-            return out
-
-        block_off = excl_cumsum(block_len)
-        ent_off_l = excl_cumsum(m["ent_cnt"].to(T.int64))
-        react_off_l = excl_cumsum(m["react_cnt"].to(T.int64))
-        com_off_l = excl_cumsum(m["com_cnt"].to(T.int64))
-        msg_total = int(block_off[-1].item())
-        E = int(ent_off_l[-1].item())
-        R = int(react_off_l[-1].item())
-        C = int(com_off_l[-1].item())
+        block_off, msg_total = gpu_mod._excl_offsets(block_len)
+        ent_off_l, E = gpu_mod._excl_offsets(m["ent_cnt"])
+        react_off_l, R = gpu_mod._excl_offsets(m["react_cnt"])
+        com_off_l, C = gpu_mod._excl_offsets(m["com_cnt"])
         cblock = max(len(b) for b in self._comment_bytes) + HANDLE_WIDTH
 
         # channel table bytes (host-small)
@@ -457,31 +438,28 @@ class SyntheticFeed:
             (0, 5), dtype=T.int32, device=device)
         ent_store = entities if E else z32(5).view(1, 5)
         react_emoji, react_count = z32(max(R, 1)), z32(max(R, 1))
-        fill_ptrs = gpu_mod._ptr_array([
-            pool, text_off, m["aux_off"], m["poster_off"], m["ent_off"],
-            m["react_off"], ent_store, react_emoji, react_count,
-        ])
+        fill_ptrs = views.bind("FeedFillOut", dict(
+            m, pool=pool, text_off=text_off, entities=ent_store,
+            react_emoji=react_emoji, react_count=react_count).get, device)
         gpu_mod._call("crawl_feed_fill", tbl_ptrs, scalars, cids_t, tidx,
                       block_off, ent_off_l, react_off_l, fill_ptrs,
                       min((N + 3) // 4, 8192))
 
         com = {f: z32(max(C, 1)) for f in [
-            "text_off", "text_len", "handle_off", "handle_len", "views",
-            "replies", "react_off", "react_cnt"]}
+            "com_text_off", "com_text_len", "com_handle_off",
+            "com_handle_len", "com_views", "com_replies", "com_react_off",
+            "com_react_cnt"]}
         if C:
             cmsg_of = T.repeat_interleave(
                 T.arange(N, dtype=T.int64, device=device),
                 m["com_cnt"].to(T.int64))
-            com_ptrs = gpu_mod._ptr_array([
-                pool, com["text_off"], com["text_len"],
-                com["handle_off"], com["handle_len"], com["views"],
-                com["replies"], com["react_off"], com["react_cnt"],
-            ])
+            com_ptrs = views.bind("FeedCommentOut",
+                                  dict(com, pool=pool).get, device)
             gpu_mod._call("crawl_feed_comments", tbl_ptrs, scalars, cids_t,
                           com_off_l, cblock, cmsg_of, msg_total, C, com_ptrs,
                           min((C + 255) // 256, 8192))
 
-        m["com_off"] = com_off_l[:-1].to(T.int32)
+        m["com_off"] = com_off_l.to(T.int32)
         t = lambda arr, dt_: T.tensor(arr, dtype=dt_, device=device)
         return B.MessageBatch(
             n=N, chat_id=chat_id, msg_id=msg_id, text_off=text_off,
@@ -489,12 +467,7 @@ class SyntheticFeed:
             entities=entities if E else T.zeros((0, 5), dtype=T.int32,
                                                 device=device),
             react_emoji=react_emoji[:R], react_count=react_count[:R],
-            com_text_off=com["text_off"][:C], com_text_len=com["text_len"][:C],
-            com_handle_off=com["handle_off"][:C],
-            com_handle_len=com["handle_len"][:C],
-            com_views=com["views"][:C], com_replies=com["replies"][:C],
-            com_react_off=com["react_off"][:C],
-            com_react_cnt=com["react_cnt"][:C],
+            **{f: col[:C] for f, col in com.items()},
             n_channels=K,
             ch_chat_id=t(np.array([r.chat_id for r in rows]), T.int64),
             ch_member=t(np.array([r.member_count for r in rows]), T.int32),

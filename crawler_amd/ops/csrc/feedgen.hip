@@ -11,6 +11,7 @@
 //   3. comment kernel: per-comment text/handle pool + rows
 
 #include "common.h"
+#include "views.h"
 
 namespace crawl {
 
@@ -22,27 +23,9 @@ DEV unsigned long long splitmix64(unsigned long long x) {
 }
 
 struct TemplateTables {
-  const unsigned char* pool;   // concatenated template pool bytes
-  const int* pool_off;         // [T]
-  const int* pool_len;         // [T]
-  const int* text_len;         // [T]
-  const int* ctype;            // [T]
-  const int* tflags;           // [T]
-  const unsigned char* aux;    // concatenated aux bytes
-  const int* aux_off;          // [T]
-  const int* aux_len;          // [T]
-  const int* ents;             // concatenated [E_t,5] rows
-  const int* ent_off;          // [T] row offset
-  const int* ent_cnt;          // [T]
-  const int* slots;            // concatenated slot byte positions
-  const int* slot_off;         // [T]
-  const int* slot_cnt;         // [T]
-  const double* cdf;           // [T]
+  TemplateTables_FIELDS_0(VIEW_MEMBER)
   int n_templates;
-  // comment text table
-  const unsigned char* ctext;  // concatenated comment texts
-  const int* ctext_off;        // [NC]
-  const int* ctext_len;        // [NC]
+  TemplateTables_FIELDS_1(VIEW_MEMBER)  // comment text table
   int n_ctexts;
 };
 
@@ -249,31 +232,15 @@ feed_comment_kernel(TemplateTables T, FeedParams F, const long* com_off_l,
   }
 }
 
+// the pointer arrays (tables and each phase's outputs) are laid out by
+// views.h
 static TemplateTables make_tables(void** p, const long* s) {
-  TemplateTables T;
+  TemplateTables V;
   int k = 0;
-  T.pool = (const unsigned char*)p[k++];
-  T.pool_off = (const int*)p[k++];
-  T.pool_len = (const int*)p[k++];
-  T.text_len = (const int*)p[k++];
-  T.ctype = (const int*)p[k++];
-  T.tflags = (const int*)p[k++];
-  T.aux = (const unsigned char*)p[k++];
-  T.aux_off = (const int*)p[k++];
-  T.aux_len = (const int*)p[k++];
-  T.ents = (const int*)p[k++];
-  T.ent_off = (const int*)p[k++];
-  T.ent_cnt = (const int*)p[k++];
-  T.slots = (const int*)p[k++];
-  T.slot_off = (const int*)p[k++];
-  T.slot_cnt = (const int*)p[k++];
-  T.cdf = (const double*)p[k++];
-  T.ctext = (const unsigned char*)p[k++];
-  T.ctext_off = (const int*)p[k++];
-  T.ctext_len = (const int*)p[k++];
-  T.n_templates = (int)s[0];
-  T.n_ctexts = (int)s[1];
-  return T;
+  TemplateTables_FIELDS(VIEW_UNPACK)
+  V.n_templates = (int)s[0];
+  V.n_ctexts = (int)s[1];
+  return V;
 }
 
 static FeedParams make_params(const long* s, const void* channel_ids) {
@@ -299,25 +266,9 @@ int crawl_feed_meta(void** tbl_ptrs, const long* scalars,
                     void* stream) {
   crawl::TemplateTables T = crawl::make_tables(tbl_ptrs, scalars);
   crawl::FeedParams F = crawl::make_params(scalars, channel_ids);
+  void** p = out_ptrs;
   int k = 0;
-  long* chat_id = (long*)out_ptrs[k++];
-  long* msg_id = (long*)out_ptrs[k++];
-  int* date = (int*)out_ptrs[k++];
-  int* content_type = (int*)out_ptrs[k++];
-  int* views = (int*)out_ptrs[k++];
-  int* forwards = (int*)out_ptrs[k++];
-  int* media_album_id = (int*)out_ptrs[k++];
-  int* channel_idx = (int*)out_ptrs[k++];
-  int* flags = (int*)out_ptrs[k++];
-  int* text_len = (int*)out_ptrs[k++];
-  int* aux_len = (int*)out_ptrs[k++];
-  int* ent_cnt = (int*)out_ptrs[k++];
-  int* react_cnt = (int*)out_ptrs[k++];
-  int* com_cnt = (int*)out_ptrs[k++];
-  int* poster_len = (int*)out_ptrs[k++];
-  int* reply_count = (int*)out_ptrs[k++];
-  long* block_len = (long*)out_ptrs[k++];
-  int* tidx = (int*)out_ptrs[k++];
+  FeedMetaOut_FIELDS(VIEW_LOCAL)
   hipLaunchKernelGGL(crawl::feed_meta_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, T, F, chat_id, msg_id, date,
                      content_type, views, forwards, media_album_id,
@@ -334,16 +285,9 @@ int crawl_feed_fill(void** tbl_ptrs, const long* scalars,
                     void* stream) {
   crawl::TemplateTables T = crawl::make_tables(tbl_ptrs, scalars);
   crawl::FeedParams F = crawl::make_params(scalars, channel_ids);
+  void** p = out_ptrs;
   int k = 0;
-  unsigned char* pool = (unsigned char*)out_ptrs[k++];
-  long* text_off = (long*)out_ptrs[k++];
-  int* aux_off = (int*)out_ptrs[k++];
-  int* poster_off = (int*)out_ptrs[k++];
-  int* ent_off = (int*)out_ptrs[k++];
-  int* react_off = (int*)out_ptrs[k++];
-  int* entities = (int*)out_ptrs[k++];
-  int* react_emoji = (int*)out_ptrs[k++];
-  int* react_count = (int*)out_ptrs[k++];
+  FeedFillOut_FIELDS(VIEW_LOCAL)
   hipLaunchKernelGGL(crawl::feed_fill_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, T, F, (const int*)tidx,
                      (const long*)block_off, (const long*)ent_off_l,
@@ -360,16 +304,9 @@ int crawl_feed_comments(void** tbl_ptrs, const long* scalars,
                         int grid, void* stream) {
   crawl::TemplateTables T = crawl::make_tables(tbl_ptrs, scalars);
   crawl::FeedParams F = crawl::make_params(scalars, channel_ids);
+  void** p = out_ptrs;
   int k = 0;
-  unsigned char* pool = (unsigned char*)out_ptrs[k++];
-  int* com_text_off = (int*)out_ptrs[k++];
-  int* com_text_len = (int*)out_ptrs[k++];
-  int* com_handle_off = (int*)out_ptrs[k++];
-  int* com_handle_len = (int*)out_ptrs[k++];
-  int* com_views = (int*)out_ptrs[k++];
-  int* com_replies = (int*)out_ptrs[k++];
-  int* com_react_off = (int*)out_ptrs[k++];
-  int* com_react_cnt = (int*)out_ptrs[k++];
+  FeedCommentOut_FIELDS(VIEW_LOCAL)
   hipLaunchKernelGGL(crawl::feed_comment_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, T, F, (const long*)com_off_l,
                      cblock, (const long*)cmsg_of,

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "tg_lits.h"
+#include "views.h"
 
 namespace crawl {
 
@@ -27,76 +28,22 @@ namespace crawl {
 // (oversize fields fall back to their global pointers)
 #define TG_STAGE_BYTES 3968
 
+// Pointer members come from views.h; the scalars between them keep the
+// kernarg layout.
 struct BatchView {
-  // per-message
-  const long* __restrict__ chat_id;
-  const long* __restrict__ msg_id;
-  const long* __restrict__ text_off;
-  const int* __restrict__ date;
-  const int* __restrict__ content_type;
-  const int* __restrict__ views;
-  const int* __restrict__ forwards;
-  const int* __restrict__ media_album_id;
-  const int* __restrict__ channel_idx;
-  const int* __restrict__ flags;
-  const int* __restrict__ text_len;
-  const int* __restrict__ aux_off;
-  const int* __restrict__ aux_len;
-  const int* __restrict__ ent_off;
-  const int* __restrict__ ent_cnt;
-  const int* __restrict__ react_off;
-  const int* __restrict__ react_cnt;
-  const int* __restrict__ com_off;
-  const int* __restrict__ com_cnt;
-  const int* __restrict__ poster_off;
-  const int* __restrict__ poster_len;
-  // pools / tables
-  const unsigned char* __restrict__ pool;
-  const int* __restrict__ entities;  // [E,5] etype,off16,len16,url_off,url_len
-  const int* __restrict__ react_emoji;
-  const int* __restrict__ react_count;
-  const int* __restrict__ com_text_off;
-  const int* __restrict__ com_text_len;
-  const int* __restrict__ com_handle_off;
-  const int* __restrict__ com_handle_len;
-  const int* __restrict__ com_views;
-  const int* __restrict__ com_replies;
-  const int* __restrict__ com_react_off;
-  const int* __restrict__ com_react_cnt;
-  // channel table
-  const long* __restrict__ ch_chat_id;
-  const int* __restrict__ ch_member;
-  const int* __restrict__ ch_postcount;
-  const int* __restrict__ ch_totalviews;
-  const int* __restrict__ ch_user_off;
-  const int* __restrict__ ch_user_len;
-  const int* __restrict__ ch_title_off;
-  const int* __restrict__ ch_title_len;
-  // emoji vocabulary
-  const unsigned char* __restrict__ emoji_pool;
-  const int* __restrict__ emoji_off;
-  const int* __restrict__ emoji_len;
-  // timestamps (preformatted Go time strings)
-  const unsigned char* __restrict__ created_str;
+  BatchView_FIELDS_0(VIEW_MEMBER)
   int created_len;
-  const unsigned char* __restrict__ capture_str;
+  BatchView_FIELDS_1(VIEW_MEMBER)
   int capture_len;
   // config
   int n;
   int skip_media;
   long min_post_date;  // unix secs; <= filters nothing when INT64_MIN
-  // content-type name table
-  const unsigned char* __restrict__ ctname_pool;
-  const int* __restrict__ ctname_off;
-  const int* __restrict__ ctname_len;
+  BatchView_FIELDS_2(VIEW_MEMBER)
 };
 
 struct LinkOut {
-  unsigned char* __restrict__ name;     // [N, MAX_LINKS, 32]
-  unsigned char* __restrict__ name_len; // [N, MAX_LINKS]
-  unsigned char* __restrict__ src;      // [N, MAX_LINKS] 0=mention 1=text_url 2=url 3=plain
-  int* __restrict__ cnt;                // [N]
-  unsigned long long* __restrict__ hash;// [N, MAX_LINKS] fnv1a64 of name
+  LinkOut_FIELDS(VIEW_MEMBER)
 };
 
 // ---------- UTF-16 offset resolution (oracle: golden.utf16_offset_to_bytes)
@@ -554,6 +501,14 @@ DEV int emit_line(const BatchView& B, int i, unsigned char* out,
 
 // ---------- kernels ----------
 
+// message i's rows of the global link arrays, holding cnt links
+DEV LinkList links_of(const LinkOut& LO, int i, int cnt) {
+  return LinkList{LO.name + (size_t)i * MAX_LINKS * 32,
+                  LO.name_len + (size_t)i * MAX_LINKS,
+                  LO.src + (size_t)i * MAX_LINKS,
+                  LO.hash + (size_t)i * MAX_LINKS, cnt};
+}
+
 __global__ void __launch_bounds__(256, 6)
 measure_extract_kernel(BatchView B, LinkOut LO, int* __restrict__ line_len) {
   __shared__ unsigned char s_lits[TG_POOL_BYTES];
@@ -609,10 +564,7 @@ write_kernel(BatchView B, LinkOut LO, const long* __restrict__ line_off,
   const int waves_per_grid = gridDim.x * 4;
   for (int i = blockIdx.x * 4 + wave; i < B.n; i += waves_per_grid) {
     if (line_len[i] == 0) continue;
-    LinkList L{LO.name + (size_t)i * MAX_LINKS * 32,
-               LO.name_len + (size_t)i * MAX_LINKS,
-               LO.src + (size_t)i * MAX_LINKS,
-               LO.hash + (size_t)i * MAX_LINKS, LO.cnt[i]};
+    LinkList L = links_of(LO, i, LO.cnt[i]);
     emit_line<true, false>(B, i, out + line_off[i], L, s_lits, nullptr,
                            nullptr);
   }
@@ -669,10 +621,7 @@ write_staged_kernel(BatchView B, LinkOut LO, const long* __restrict__ line_off,
   const int waves_per_grid = gridDim.x * 4;
   for (int i = blockIdx.x * 4 + wave; i < B.n; i += waves_per_grid) {
     if (line_len[i] == 0) continue;
-    LinkList L{LO.name + (size_t)i * MAX_LINKS * 32,
-               LO.name_len + (size_t)i * MAX_LINKS,
-               LO.src + (size_t)i * MAX_LINKS,
-               LO.hash + (size_t)i * MAX_LINKS, LO.cnt[i]};
+    LinkList L = links_of(LO, i, LO.cnt[i]);
     emit_line<true, true>(B, i, out + line_off[i], L, s_lits,
                           &s_stage[wave][0], &T);
   }
@@ -706,10 +655,7 @@ write_lds_kernel(BatchView B, LinkOut LO, const long* __restrict__ line_off,
   for (int i = blockIdx.x * 4 + wave; i < B.n; i += waves_per_grid) {
     const int len = line_len[i];
     if (len == 0) continue;
-    LinkList L{LO.name + (size_t)i * MAX_LINKS * 32,
-               LO.name_len + (size_t)i * MAX_LINKS,
-               LO.src + (size_t)i * MAX_LINKS,
-               LO.hash + (size_t)i * MAX_LINKS, LO.cnt[i]};
+    LinkList L = links_of(LO, i, LO.cnt[i]);
     if (len > LDS_LINE_BYTES) {
       emit_line<true, false>(B, i, out + line_off[i], L, s_lits,
                              nullptr, nullptr);
@@ -741,10 +687,7 @@ write_scratch_kernel(BatchView B, LinkOut LO, unsigned char* __restrict__ scratc
       if (lane == 0) { line_len[i] = 0; LO.cnt[i] = 0; }
       continue;
     }
-    LinkList L{LO.name + (size_t)i * MAX_LINKS * 32,
-               LO.name_len + (size_t)i * MAX_LINKS,
-               LO.src + (size_t)i * MAX_LINKS,
-               LO.hash + (size_t)i * MAX_LINKS, 0};
+    LinkList L = links_of(LO, i, 0);
     extract_links(B, i, L, lane);
     int len = emit_line<true, false>(B, i, scratch + (size_t)i * stride, L,
                                      s_lits, nullptr, nullptr);
@@ -803,93 +746,51 @@ compact_kernel(const unsigned char* scratch, long stride,
 
 // ---- C ABI (ctypes-friendly; torch-header-free) ----
 //
-// Pointer/scalar array layouts MUST stay in sync with ops/gpu.py
-// (_BATCH_PTR_ORDER, and the ``scalars`` array parse_encode builds). The
-// Python side passes tensor.data_ptr() values in that order.
+// The pointer arrays are laid out by views.h (ops/views.py packs them
+// from the same file); ``scalars`` is the array parse_encode builds.
 
 namespace crawl {
 
 static BatchView make_view(void** p, const long* s) {
-  BatchView B;
+  BatchView V;
   int k = 0;
-  B.chat_id = (const long*)p[k++];
-  B.msg_id = (const long*)p[k++];
-  B.text_off = (const long*)p[k++];
-  B.date = (const int*)p[k++];
-  B.content_type = (const int*)p[k++];
-  B.views = (const int*)p[k++];
-  B.forwards = (const int*)p[k++];
-  B.media_album_id = (const int*)p[k++];
-  B.channel_idx = (const int*)p[k++];
-  B.flags = (const int*)p[k++];
-  B.text_len = (const int*)p[k++];
-  B.aux_off = (const int*)p[k++];
-  B.aux_len = (const int*)p[k++];
-  B.ent_off = (const int*)p[k++];
-  B.ent_cnt = (const int*)p[k++];
-  B.react_off = (const int*)p[k++];
-  B.react_cnt = (const int*)p[k++];
-  B.com_off = (const int*)p[k++];
-  B.com_cnt = (const int*)p[k++];
-  B.poster_off = (const int*)p[k++];
-  B.poster_len = (const int*)p[k++];
-  B.pool = (const unsigned char*)p[k++];
-  B.entities = (const int*)p[k++];
-  B.react_emoji = (const int*)p[k++];
-  B.react_count = (const int*)p[k++];
-  B.com_text_off = (const int*)p[k++];
-  B.com_text_len = (const int*)p[k++];
-  B.com_handle_off = (const int*)p[k++];
-  B.com_handle_len = (const int*)p[k++];
-  B.com_views = (const int*)p[k++];
-  B.com_replies = (const int*)p[k++];
-  B.com_react_off = (const int*)p[k++];
-  B.com_react_cnt = (const int*)p[k++];
-  B.ch_chat_id = (const long*)p[k++];
-  B.ch_member = (const int*)p[k++];
-  B.ch_postcount = (const int*)p[k++];
-  B.ch_totalviews = (const int*)p[k++];
-  B.ch_user_off = (const int*)p[k++];
-  B.ch_user_len = (const int*)p[k++];
-  B.ch_title_off = (const int*)p[k++];
-  B.ch_title_len = (const int*)p[k++];
-  B.emoji_pool = (const unsigned char*)p[k++];
-  B.emoji_off = (const int*)p[k++];
-  B.emoji_len = (const int*)p[k++];
-  B.created_str = (const unsigned char*)p[k++];
-  B.capture_str = (const unsigned char*)p[k++];
-  B.ctname_pool = (const unsigned char*)p[k++];
-  B.ctname_off = (const int*)p[k++];
-  B.ctname_len = (const int*)p[k++];
-  B.n = (int)s[0];
-  B.skip_media = (int)s[1];
-  B.min_post_date = s[2];
-  B.created_len = (int)s[3];
-  B.capture_len = (int)s[4];
-  return B;
+  BatchView_FIELDS(VIEW_UNPACK)
+  V.n = (int)s[0];
+  V.skip_media = (int)s[1];
+  V.min_post_date = s[2];
+  V.created_len = (int)s[3];
+  V.capture_len = (int)s[4];
+  return V;
 }
 
 static LinkOut make_links(void** p) {
-  LinkOut L;
-  L.name = (unsigned char*)p[0];
-  L.name_len = (unsigned char*)p[1];
-  L.src = (unsigned char*)p[2];
-  L.cnt = (int*)p[3];
-  L.hash = (unsigned long long*)p[4];
-  return L;
+  LinkOut V;
+  int k = 0;
+  LinkOut_FIELDS(VIEW_UNPACK)
+  return V;
+}
+
+// what every parse/encode entry point starts from
+struct Views {
+  BatchView B;
+  LinkOut LO;
+};
+
+static Views make_views(void** batch_ptrs, const long* scalars,
+                        void** link_ptrs) {
+  return {make_view(batch_ptrs, scalars), make_links(link_ptrs)};
 }
 
 }  // namespace crawl
 
 extern "C" {
 
-int crawl_batch_ptr_count() { return 49; }
+int crawl_batch_ptr_count() { return 0 BatchView_FIELDS(VIEW_COUNT); }
 
 int crawl_measure_extract(void** batch_ptrs, const long* scalars,
                           void** link_ptrs, void* line_len, int grid,
                           void* stream) {
-  crawl::BatchView B = crawl::make_view(batch_ptrs, scalars);
-  crawl::LinkOut LO = crawl::make_links(link_ptrs);
+  auto [B, LO] = crawl::make_views(batch_ptrs, scalars, link_ptrs);
   hipLaunchKernelGGL(crawl::measure_extract_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, B, LO, (int*)line_len);
   return (int)hipGetLastError();
@@ -898,8 +799,7 @@ int crawl_measure_extract(void** batch_ptrs, const long* scalars,
 int crawl_write(void** batch_ptrs, const long* scalars, void** link_ptrs,
                 const void* line_off, const void* line_len, void* out,
                 int grid, void* stream) {
-  crawl::BatchView B = crawl::make_view(batch_ptrs, scalars);
-  crawl::LinkOut LO = crawl::make_links(link_ptrs);
+  auto [B, LO] = crawl::make_views(batch_ptrs, scalars, link_ptrs);
   hipLaunchKernelGGL(crawl::write_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, B, LO, (const long*)line_off,
                      (const int*)line_len, (unsigned char*)out);
@@ -912,8 +812,7 @@ int crawl_write_staged(void** batch_ptrs, const long* scalars,
                        int n_emoji, int emoji_pool_bytes,
                        int n_ctnames, int ctname_pool_bytes,
                        int grid, void* stream) {
-  crawl::BatchView B = crawl::make_view(batch_ptrs, scalars);
-  crawl::LinkOut LO = crawl::make_links(link_ptrs);
+  auto [B, LO] = crawl::make_views(batch_ptrs, scalars, link_ptrs);
   hipLaunchKernelGGL(crawl::write_staged_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, B, LO, (const long*)line_off,
                      (const int*)line_len, (unsigned char*)out,
@@ -930,8 +829,7 @@ int crawl_write_scratch(void** batch_ptrs, const long* scalars,
                         void** link_ptrs, void* scratch, long stride,
                         void* line_len, void* overflow, int grid,
                         void* stream) {
-  crawl::BatchView B = crawl::make_view(batch_ptrs, scalars);
-  crawl::LinkOut LO = crawl::make_links(link_ptrs);
+  auto [B, LO] = crawl::make_views(batch_ptrs, scalars, link_ptrs);
   hipLaunchKernelGGL(crawl::write_scratch_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, B, LO, (unsigned char*)scratch,
                      stride, (int*)line_len, (int*)overflow);
@@ -941,8 +839,7 @@ int crawl_write_scratch(void** batch_ptrs, const long* scalars,
 int crawl_write_lds(void** batch_ptrs, const long* scalars, void** link_ptrs,
                     const void* line_off, const void* line_len, void* out,
                     int grid, void* stream) {
-  crawl::BatchView B = crawl::make_view(batch_ptrs, scalars);
-  crawl::LinkOut LO = crawl::make_links(link_ptrs);
+  auto [B, LO] = crawl::make_views(batch_ptrs, scalars, link_ptrs);
   hipLaunchKernelGGL(crawl::write_lds_kernel, dim3(grid), dim3(256), 0,
                      (hipStream_t)stream, B, LO, (const long*)line_off,
                      (const int*)line_len, (unsigned char*)out);

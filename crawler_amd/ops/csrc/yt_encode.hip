@@ -10,40 +10,16 @@
 // crawler_amd/youtube/batch.py encode_yt_batch).
 
 #include "common.h"
+#include "views.h"
 
 namespace crawl {
 
 struct YtView {
-  const int* vid_off;
-  const int* channel_idx;
-  const long* published;
-  const long* views;
-  const int* likes;
-  const int* comments;
-  const int* duration_s;
-  const int* lang;
-  const long* title_off;
-  const int* title_len;
-  const long* desc_off;
-  const int* desc_len;
-  const unsigned char* pool;
-  const int* ch_id_off;
-  const int* ch_title_off;
-  const int* ch_title_len;
-  const int* ch_desc_off;
-  const int* ch_desc_len;
-  const long* ch_subs;
-  const int* ch_videos;
-  const long* ch_views;
-  const int* ch_country_off;
-  const int* ch_country_len;
-  const long* ch_published;
-  const unsigned char* label;
+  YtView_FIELDS_0(VIEW_MEMBER)
   int label_len;
-  const unsigned char* lang_pool;  // "enru"
-  const unsigned char* created_str;
+  YtView_FIELDS_1(VIEW_MEMBER)
   int created_len;
-  const unsigned char* capture_str;
+  YtView_FIELDS_2(VIEW_MEMBER)
   int capture_len;
   int n;
 };
@@ -334,49 +310,23 @@ yt_write_kernel(YtView B, const long* line_off, unsigned char* out) {
   }
 }
 
+// the pointer array is laid out by views.h
 static YtView yt_make_view(void** p, const long* s) {
-  YtView B;
+  YtView V;
   int k = 0;
-  B.vid_off = (const int*)p[k++];
-  B.channel_idx = (const int*)p[k++];
-  B.published = (const long*)p[k++];
-  B.views = (const long*)p[k++];
-  B.likes = (const int*)p[k++];
-  B.comments = (const int*)p[k++];
-  B.duration_s = (const int*)p[k++];
-  B.lang = (const int*)p[k++];
-  B.title_off = (const long*)p[k++];
-  B.title_len = (const int*)p[k++];
-  B.desc_off = (const long*)p[k++];
-  B.desc_len = (const int*)p[k++];
-  B.pool = (const unsigned char*)p[k++];
-  B.ch_id_off = (const int*)p[k++];
-  B.ch_title_off = (const int*)p[k++];
-  B.ch_title_len = (const int*)p[k++];
-  B.ch_desc_off = (const int*)p[k++];
-  B.ch_desc_len = (const int*)p[k++];
-  B.ch_subs = (const long*)p[k++];
-  B.ch_videos = (const int*)p[k++];
-  B.ch_views = (const long*)p[k++];
-  B.ch_country_off = (const int*)p[k++];
-  B.ch_country_len = (const int*)p[k++];
-  B.ch_published = (const long*)p[k++];
-  B.label = (const unsigned char*)p[k++];
-  B.lang_pool = (const unsigned char*)p[k++];
-  B.created_str = (const unsigned char*)p[k++];
-  B.capture_str = (const unsigned char*)p[k++];
-  B.n = (int)s[0];
-  B.label_len = (int)s[1];
-  B.created_len = (int)s[2];
-  B.capture_len = (int)s[3];
-  return B;
+  YtView_FIELDS(VIEW_UNPACK)
+  V.n = (int)s[0];
+  V.label_len = (int)s[1];
+  V.created_len = (int)s[2];
+  V.capture_len = (int)s[3];
+  return V;
 }
 
 }  // namespace crawl
 
 extern "C" {
 
-int crawl_yt_ptr_count() { return 28; }
+int crawl_yt_ptr_count() { return 0 YtView_FIELDS(VIEW_COUNT); }
 
 int crawl_yt_measure(void** ptrs, const long* scalars, void* line_len,
                      int grid, void* stream) {

@@ -17,26 +17,12 @@ import torch
 
 from ..models.post import format_go_time
 from . import batch as B
+from . import views
 
 _CSRC = os.path.dirname(os.path.abspath(__file__)) + "/csrc"
 _LIB_PATH = os.path.join(_CSRC, "libcrawlhip.so")
 
 MAX_LINKS = 8
-
-# Must match crawl::make_view() field order in csrc/parse_encode.hip.
-_BATCH_PTR_ORDER = [
-    "chat_id", "msg_id", "text_off",
-    # meta int32 fields, in BatchView order:
-    "m:date", "m:content_type", "m:views", "m:forwards", "m:media_album_id",
-    "m:channel_idx", "m:flags", "m:text_len", "m:aux_off", "m:aux_len",
-    "m:ent_off", "m:ent_cnt", "m:react_off", "m:react_cnt", "m:com_off",
-    "m:com_cnt", "m:poster_off", "m:poster_len",
-    "text_pool", "entities", "react_emoji", "react_count",
-    "com_text_off", "com_text_len", "com_handle_off", "com_handle_len",
-    "com_views", "com_replies", "com_react_off", "com_react_cnt",
-    "ch_chat_id", "ch_member", "ch_postcount", "ch_totalviews",
-    "ch_user_off", "ch_user_len", "ch_title_off", "ch_title_len",
-]
 
 _lib = None
 
@@ -161,14 +147,19 @@ def _call(name: str, *args, stream: Optional[torch.cuda.Stream] = None):
         raise RuntimeError(f"{name} failed: hip {rc}")
 
 
-# Must match crawl::yt_make_view() in csrc/yt_encode.hip.
-_YT_PTR_ORDER = [
-    "vid_off", "channel_idx", "published", "views", "likes", "comments",
-    "duration_s", "lang", "title_off", "title_len", "desc_off", "desc_len",
-    "pool", "ch_id_off", "ch_title_off", "ch_title_len", "ch_desc_off",
-    "ch_desc_len", "ch_subs", "ch_videos", "ch_views", "ch_country_off",
-    "ch_country_len", "ch_published",
-]
+def _excl_offsets(lengths: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """Measure-then-place: (int64 exclusive offsets, host total) of integer
+    ``lengths``, with one host sync (none for empty input)."""
+    end = torch.cumsum(lengths, 0, dtype=torch.int64)
+    return end - lengths, int(end[-1].item()) if lengths.numel() else 0
+
+
+def _kp_shape(batch: B.MessageBatch) -> Tuple[int, int]:
+    """(K, P) of a K x P channel-grouped batch."""
+    K = batch.n_channels
+    P = batch.n // K if K else 0
+    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    return K, P
 
 
 class YtEncodeResult(tuple):
@@ -208,15 +199,13 @@ def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
     capture = format_go_time(now).encode()
     to_dev = lambda b: torch.frombuffer(bytearray(b or b"\0"),
                                         dtype=torch.uint8).to(dev)
-    label_t = to_dev(batch.crawl_label.encode())
     from ..youtube.batch import LANGS
 
-    lang_t = to_dev("".join(LANGS).encode())
-    created_t, capture_t = to_dev(created), to_dev(capture)
-    tensors = [getattr(batch, name) for name in _YT_PTR_ORDER]
-    tensors += [label_t, lang_t, created_t, capture_t]
-    ptrs = _ptr_array(tensors)
-    assert len(tensors) == lib.crawl_yt_ptr_count()
+    extras = {"label": to_dev(batch.crawl_label.encode()),
+              "lang_pool": to_dev("".join(LANGS).encode()),
+              "created_str": to_dev(created), "capture_str": to_dev(capture)}
+    ptrs = views.bind("YtView", views.lookup_in(batch, extras), dev)
+    assert len(ptrs) == lib.crawl_yt_ptr_count(), "library older than views.h"
     scalars = (ctypes.c_long * 4)(
         n, len(batch.crawl_label.encode()), len(created), len(capture)
     )
@@ -224,9 +213,7 @@ def yt_parse_encode(batch, now: Optional[_dt.datetime] = None,
         grid = min((n + 3) // 4, 8192)
     line_len = torch.zeros(n, dtype=torch.int32, device=dev)
     _call("crawl_yt_measure", ptrs, scalars, line_len, grid)
-    line_off = torch.zeros(n, dtype=torch.int64, device=dev)
-    torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
-    total = int(line_off[-1].item() + line_len[-1].item())
+    line_off, total = _excl_offsets(line_len)
     out, raw = _alloc_out(total, dev, _poison, _guard)
     _call("crawl_yt_write", ptrs, scalars, line_off, out, grid)
     return YtEncodeResult(out, line_off, line_len, raw)
@@ -402,10 +389,7 @@ def yt_scan_channel_ids(pool: torch.Tensor, text_off: torch.Tensor,
     if bool(bad.item()):
         raise ValueError("a text range lies outside the pool")
     _call("crawl_yt_scan_count", pool, text_off, text_len, n, counts)
-    c64 = counts.to(torch.int64)
-    end = torch.cumsum(c64, 0)
-    out_base = (end - c64).contiguous()
-    total = int(end[-1].item())
+    out_base, total = _excl_offsets(counts)
     hit_off = torch.empty(total, dtype=torch.int64, device=dev)
     if total:
         _call("crawl_yt_scan_write", pool, text_off, text_len, n, out_base,
@@ -479,9 +463,7 @@ def channel_stats(batch: B.MessageBatch, line_len=None):
     into ``totals``, so the driver hands it zeros. A batch without
     channels gives empty outputs and no launch."""
     dev = batch.device
-    K = batch.n_channels
-    P = batch.n // K if K else 0
-    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    K, P = _kp_shape(batch)
     if line_len is not None:
         if (line_len.dtype != torch.int32 or line_len.numel() != batch.n
                 or line_len.device != dev):
@@ -511,9 +493,7 @@ def reservoir_sample(batch: B.MessageBatch, k: int, seed: int = 0):
     (device): a channel with no more than ``k`` rows keeps all of them,
     as the reference does (telegramutils.go:124)."""
     dev = batch.device
-    K = batch.n_channels
-    P = batch.n // K if K else 0
-    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    K, P = _kp_shape(batch)
     if k < 0:
         raise ValueError("the sample size must not be negative")
     k = min(k, P)
@@ -586,20 +566,11 @@ def fetch_window(batch: B.MessageBatch, stop_below: Optional[int] = None,
     (off by default): the guarded buffers are the result's ``.raw_keep``
     and ``.raw_kept`` (``_guard`` counts elements)."""
     dev = batch.device
-    K = batch.n_channels
-    P = batch.n // K if K else 0
-    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    K, P = _kp_shape(batch)
     if cap < 0 or sample_k < 0:
         raise ValueError("cap and sample_k must not be negative")
     keep, raw_keep = _alloc_out(batch.n, dev, _poison, _guard)
-    if _poison is None and _guard <= 0:
-        kept, raw_kept = torch.empty(K, dtype=torch.int32, device=dev), None
-    else:
-        g = max(_guard, 0)
-        fill = 0xA5 if _poison is None else _poison
-        raw_kept = torch.full((4 * (K + 2 * g),), fill, dtype=torch.uint8,
-                              device=dev).view(torch.int32)
-        kept = raw_kept[g:g + K]
+    kept, raw_kept = _alloc_out(K, dev, _poison, _guard, torch.int32)
     if K == 0:
         return FetchWindowResult(keep, kept, raw_keep, raw_kept)
     from .golden_window import NO_SKIP, NO_STOP
@@ -670,9 +641,7 @@ def _grouped_shape(batch: B.MessageBatch, keep, kept):
     """(K, P) of a K x P channel-grouped batch, after checking a
     fetch-window result against it."""
     dev = batch.device
-    K = batch.n_channels
-    P = batch.n // K if K else 0
-    assert K * P == batch.n, "batch must be K x P channel-grouped"
+    K, P = _kp_shape(batch)
     for nm, t, dt_, n in (("keep", keep, torch.uint8, batch.n),
                           ("kept", kept, torch.int32, K)):
         assert t.dtype == dt_ and t.device == dev and t.is_contiguous(), nm
@@ -698,13 +667,8 @@ def channel_gate(batch: B.MessageBatch, keep: torch.Tensor,
     all-inactive outputs and no launch."""
     dev = batch.device
     K, P = _grouped_shape(batch, keep, kept)
-    if _poison is None:
-        active = torch.empty(K, dtype=torch.uint8, device=dev)
-        latest = torch.empty(K, dtype=torch.int32, device=dev)
-    else:
-        active = torch.full((K,), _poison, dtype=torch.uint8, device=dev)
-        latest = torch.full((4 * K,), _poison, dtype=torch.uint8,
-                            device=dev).view(torch.int32)
+    active, _ = _alloc_out(K, dev, _poison, 0)
+    latest, _ = _alloc_out(K, dev, _poison, 0, torch.int32)
     if K == 0 or P == 0:
         active.zero_()
         latest.zero_()
@@ -741,14 +705,8 @@ def compact_rows(batch: B.MessageBatch, keep: torch.Tensor,
             raise ValueError("kept must not be negative")
         torch.cumsum(kept, 0, dtype=torch.int64, out=kept_offset[1:])
     total = int(kept_offset[-1].item())
-    if _poison is None:
-        rows = torch.empty(total, dtype=torch.int64, device=dev)
-        row_channel = torch.empty(total, dtype=torch.int32, device=dev)
-    else:
-        rows = torch.full((8 * total,), _poison, dtype=torch.uint8,
-                          device=dev).view(torch.int64)
-        row_channel = torch.full((4 * total,), _poison, dtype=torch.uint8,
-                                 device=dev).view(torch.int32)
+    rows, _ = _alloc_out(total, dev, _poison, 0, torch.int64)
+    row_channel, _ = _alloc_out(total, dev, _poison, 0, torch.int32)
     if total == 0:
         return rows, row_channel
     _call("crawl_compact_rows", keep, kept_offset, P, K, rows, row_channel,
@@ -854,13 +812,6 @@ class EncodeResult:
     writer: str = ""         # staged | plain | lds | scratch ("" = no launch)
     # test seam: the guarded allocation ``out`` is a view into (_guard > 0)
     raw: Optional[torch.Tensor] = None
-
-
-def _ptr_array(tensors: List[torch.Tensor]):
-    arr = (ctypes.c_void_p * len(tensors))()
-    for k, t in enumerate(tensors):
-        arr[k] = ctypes.c_void_p(t.data_ptr())
-    return arr
 
 
 def _stride_bound(batch: B.MessageBatch) -> int:
@@ -979,22 +930,23 @@ def _pick_writer(env, single_pass: bool, stage_need: Optional[int],
     return "plain"
 
 
-def _alloc_out(total: int, dev, poison: Optional[int], guard: int):
-    """Output allocation: (out, raw). With the test seams off this is a
-    bare torch.empty and raw is None. ``guard`` > 0 places ``out`` inside
-    a larger buffer with ``guard`` poisoned bytes on each side (raw is
-    that buffer); ``poison`` fills the line bytes too, so a writer that
-    skips a byte cannot inherit a stale correct one from the allocator."""
+def _alloc_out(total: int, dev, poison: Optional[int], guard: int,
+               dtype=torch.uint8):
+    """Output allocation: (out, raw) of ``total`` elements. With the test
+    seams off this is a bare torch.empty and raw is None. ``guard`` > 0
+    places ``out`` inside a larger buffer with ``guard`` poisoned elements
+    on each side (raw is that buffer); ``poison`` fills every byte of
+    ``out`` too, so a writer that skips one cannot inherit a stale correct
+    value from the allocator."""
     if poison is None and guard <= 0:
-        return torch.empty(total, dtype=torch.uint8, device=dev), None
+        return torch.empty(total, dtype=dtype, device=dev), None
     guard = max(guard, 0)
-    fill = 0xA5 if poison is None else poison
-    raw = torch.empty(total + 2 * guard, dtype=torch.uint8, device=dev)
+    raw = torch.empty(total + 2 * guard, dtype=dtype, device=dev)
     if poison is not None:
-        raw.fill_(fill)
+        raw.view(torch.uint8).fill_(poison)
     else:
-        raw[:guard].fill_(fill)
-        raw[guard + total:].fill_(fill)
+        raw[:guard].view(torch.uint8).fill_(0xA5)
+        raw[guard + total:].view(torch.uint8).fill_(0xA5)
     return raw[guard:guard + total], raw
 
 
@@ -1052,26 +1004,11 @@ def parse_encode(
     created_t = torch.frombuffer(bytearray(created), dtype=torch.uint8).to(dev)
     capture_t = torch.frombuffer(bytearray(capture), dtype=torch.uint8).to(dev)
 
-    tensors = []
-    for name in _BATCH_PTR_ORDER:
-        if name.startswith("m:"):
-            tensors.append(batch.meta[name[2:]])
-        else:
-            tensors.append(getattr(batch, name))
-    tensors += [
-        tables["emoji_pool"], tables["emoji_off"], tables["emoji_len"],
-        created_t, capture_t,
-        tables["ctname_pool"], tables["ctname_off"], tables["ctname_len"],
-    ]
-    names = _BATCH_PTR_ORDER + [
-        "emoji_pool", "emoji_off", "emoji_len", "created", "capture",
-        "ctname_pool", "ctname_off", "ctname_len",
-    ]
-    for nm, t in zip(names, tensors):
-        assert t.device == dev, f"{nm} on {t.device}, batch on {dev}"
-        assert t.is_contiguous(), f"{nm} not contiguous"
-    batch_ptrs = _ptr_array(tensors)
-    assert len(tensors) == lib.crawl_batch_ptr_count()
+    extras = dict(tables, pool=batch.text_pool, created_str=created_t,
+                  capture_str=capture_t)
+    batch_ptrs = views.bind("BatchView", views.lookup_in(batch, extras), dev)
+    assert len(batch_ptrs) == lib.crawl_batch_ptr_count(), \
+        "library older than views.h"
 
     if min_post_date is not None:
         mpd = int(min_post_date.timestamp())
@@ -1085,7 +1022,9 @@ def parse_encode(
     link_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
     link_hash = torch.zeros((n, MAX_LINKS), dtype=torch.int64, device=dev)
     line_len = torch.zeros(n, dtype=torch.int32, device=dev)
-    link_ptrs = _ptr_array([link_name, link_len, link_src, link_cnt, link_hash])
+    link_ptrs = views.bind("LinkOut", {
+        "name": link_name, "name_len": link_len, "src": link_src,
+        "cnt": link_cnt, "hash": link_hash}.get, dev)
 
     if grid <= 0:
         grid = min((n + 3) // 4, 8192)
@@ -1106,9 +1045,7 @@ def parse_encode(
         overflow = torch.zeros(1, dtype=torch.int32, device=dev)
         _call("crawl_write_scratch", batch_ptrs, scalars, link_ptrs, scratch,
               stride, line_len, overflow, grid, stream=stream)
-        line_off = torch.zeros(n, dtype=torch.int64, device=dev)
-        torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
-        total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
+        line_off, total = _excl_offsets(line_len)
         ovf = int(overflow.item())
         if ovf:
             raise RuntimeError(
@@ -1121,9 +1058,7 @@ def parse_encode(
     else:
         _call("crawl_measure_extract", batch_ptrs, scalars, link_ptrs,
               line_len, grid, stream=stream)
-        line_off = torch.zeros(n, dtype=torch.int64, device=dev)
-        torch.cumsum(line_len.to(torch.int64)[:-1], 0, out=line_off[1:])
-        total = int(line_off[-1].item() + line_len[-1].item()) if n else 0
+        line_off, total = _excl_offsets(line_len)
         out, raw = _alloc_out(total, dev, _poison, _guard)
         if writer == "staged":
             # staged writer: escape-scanned fields + reactions +
